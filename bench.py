@@ -11,9 +11,11 @@ N>1: expert-parallel (competesmoe_amd.ep): experts sharded E/N per rank, T token
 all-to-all over xGMI for dispatch/combine; launched by torch.distributed.run, one rank per GPU.
 
 Prints ONE JSON line on rank 0 (see the driver contract): value = total tokens / max-over-ranks time of K steps.
-`roofline` is for the dominant kernel (the grouped expert GEMM family): algorithmic FLOPs per launch / mean launch
-duration from HIP events recorded on the launch stream inside the timed region.  `cpu_baseline` times the CPU oracle
-(oracle/moe_oracle.py, a port of the reference layer) on a bounded sample on this host's cores (rank 0, N=1 only).
+A plain run does only that: set-up, warm-up, the K timed steps, the line.  `--full` adds what the headline figure does not
+need: `kernels` and `roofline` (the dominant kernel, i.e. the grouped expert GEMM family: algorithmic FLOPs per launch / mean
+launch duration from HIP events recorded on the launch stream inside the timed region), and `cpu_baseline`, which times the
+CPU oracle (oracle/moe_oracle.py, a port of the reference layer) on a bounded sample on this host's cores (rank 0, N=1 only).
+`--dump-outputs DIR` writes what the last timed step computed (rank 0) as float32 .npy files, see dump_outputs.
 """
 import argparse
 import json
@@ -21,6 +23,7 @@ import os
 import sys
 import time
 import types
+import zlib
 
 import torch
 import torch.nn as nn
@@ -28,8 +31,8 @@ import torch.nn as nn
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-MFMA_BF16_PEAK_TFLOPS = 2500.0   # dense bf16 peak, /opt/skills/guides/MI355X_MICROARCH.md
-MFMA_FP8_PEAK_TFLOPS = 5000.0    # dense block-scaled fp8 peak, same guide
+MFMA_BF16_PEAK_TFLOPS = 2500.0   # dense bf16 peak of the MI355X
+MFMA_FP8_PEAK_TFLOPS = 5000.0    # dense block-scaled fp8 peak of the MI355X
 HBM_PEAK_GBS = 8000.0
 ROUND = "r03"                    # profiles/<ROUND>/traffic.json holds the PMC passes of THIS round's kernels (see traffic_for)
 
@@ -100,7 +103,13 @@ def parse():
                          "steps then model the micro-batches after the first of a gradient-accumulation step).  Off by default: every step quantises")
     ap.add_argument("--shared", type=int, default=0, help="number of shared experts (width n x d_ff) of the deepseekv2 layer (fp8 / --stack pretrain)")
     ap.add_argument("--skew", action="store_true", help="add +2.0 to 8 gate rows (Zipf-like load, BASELINE.md)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-kernel table and roofline of the timed steps "
+                         "(HIP events around every launch; with --graph from eager steps before the capture) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (outputs, loss, input and parameter gradients; rank 0) "
+                         "as DIR/<name>.npy in float32, a fixed seeded sample of the larger arrays, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-tokens", type=int, default=4096)
     ap.add_argument("--graph", action="store_true", help="time REPLAYS of the step captured as one hipGraph (competesmoe_amd.graphs.GraphedStep): the launch-bound small shapes; the per-kernel table comes from eager steps run before the capture")
     ap.add_argument("--competition", action="store_true", help="time the CompeteSMoE competition step (every expert dense + sparse recompute) instead of the sparse smoe step")
@@ -248,6 +257,36 @@ def cpu_baseline(a):
                       f"(min {min(times) * 1e3:.1f}, max {max(times) * 1e3:.1f})"}
 
 
+DUMP_BYTES = 60 * 10 ** 6      # array bytes of one --dump-outputs set; the .npy headers keep the files well under 64 MB
+
+
+def dump_outputs(path, outputs, params):
+    """--dump-outputs: `outputs` (name -> tensor: what the step returns and the gradient of its input) and the gradients of
+    `params` ((name, parameter) pairs) as <path>/<name>.npy in float32.  Half the budget goes to the outputs, half to the
+    gradients; within each half an array that fits its fair share is written whole, a larger one as a sample of its flattened
+    elements at sorted indices drawn by a generator seeded from its name, the same in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    grads = {f"grad.{n}": p.grad for n, p in params if p.grad is not None}
+    files = nbytes = 0
+    for group in (outputs, grads):
+        left = DUMP_BYTES // 2 // 4
+        items = sorted(group.items(), key=lambda kv: kv[1].numel())
+        for i, (name, t) in enumerate(items):
+            t = t.detach()
+            k = min(t.numel(), left // (len(items) - i))
+            if k < t.numel():
+                g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+                idx = torch.randint(t.numel(), (k,), generator=g).sort().values
+                t = t.reshape(-1)[idx.to(t.device)]
+            a = t.float().cpu().numpy()
+            np.save(os.path.join(path, name + ".npy"), a)
+            left -= k
+            files += 1
+            nbytes += a.nbytes
+    return {"dir": path, "files": files, "bytes": nbytes}
+
+
 def free_port():
     import socket
     with socket.socket() as s:
@@ -322,6 +361,8 @@ def main():
         return stub_main(a, rank, world)
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
+    # parameters drawn from the process RNG (the pretrain-stack layers) and the competition schedule: the same on every run
+    torch.manual_seed(rank)
     if a.dtype == "fp8":
         a.stack = "pretrain"
     dt = torch.float32 if a.dtype == "fp32" else torch.bfloat16
@@ -401,7 +442,7 @@ def main():
             if g is None:
                 g = dy_as[out.dtype] = dy32.to(out.dtype)
             torch.autograd.backward([out, reg.float()], [g, one])
-            return
+            return {"out": out, "reg_loss": reg, "x_grad": x32.grad}
         if blk is not None:
             out, aux, _, _ = blk(x)
         elif ln is not None:
@@ -411,6 +452,7 @@ def main():
         else:
             out, aux, _, _ = layer(x)
         torch.autograd.backward([out, aux.float()], [dy, one])
+        return {"out": out, "aux_loss": aux, "x_grad": x.grad}
 
     def fence():
         if world > 1:
@@ -442,15 +484,17 @@ def main():
     for _ in range(a.warmup):
         step()
     fence()
+    prof = None
     if a.graph:
         assert world == 1 and a.stack == "llava" and blk is None and ln is None and not a.force_ep, "--graph: single-GPU LLaVA-stack layer only"
         from competesmoe_amd.graphs import GraphedStep
-        ops.profile_start()
-        for _ in range(min(5, a.steps)):
-            step()
-        fence()
-        prof = ops.profile_stop()
-        prof = {k: {**v, "calls": v["calls"] * a.steps / min(5, a.steps)} for k, v in prof.items()}       # per-step counts of the table below
+        if a.full:
+            ops.profile_start()
+            for _ in range(min(5, a.steps)):
+                step()
+            fence()
+            prof = ops.profile_stop()
+            prof = {k: {**v, "calls": v["calls"] * a.steps / min(5, a.steps)} for k, v in prof.items()}       # per-step counts of the table below
         x.grad = None
         for p in layer.parameters():
             p.grad = None
@@ -467,14 +511,18 @@ def main():
             gstep(x)
         fence()
         el = time.perf_counter() - t0
+        last = {"loss": gstep.outputs, "x_grad": gstep.input_grads[0]}
     else:
-        ops.profile_start()
+        if a.full:
+            ops.profile_start()
         t0 = time.perf_counter()
-        for _ in range(a.steps):
+        for _ in range(a.steps - 1):
             step()
+        last = step() if a.steps > 0 else None      # only the last step's results are kept (for --dump-outputs)
         fence()
         el = time.perf_counter() - t0
-        prof = ops.profile_stop()
+        if a.full:
+            prof = ops.profile_stop()
     if world > 1:
         tt = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -483,7 +531,15 @@ def main():
     total_tokens = Bsz * Nseq * world
 
     if rank == 0:
-        # ---- roofline of the dominant kernel family (grouped expert GEMM): FLOPs per launch / mean launch duration
+        dumped = None
+        if a.dump_outputs:
+            if blk is not None:
+                named = list(blk.named_parameters())
+            else:
+                named = list(layer.named_parameters()) + ([("ln." + n, p) for n, p in ln.named_parameters()] if ln is not None else [])
+            dumped = dump_outputs(a.dump_outputs, {k: v for k, v in last.items() if v is not None}, named)
+        # ---- (--full) roofline of the dominant kernel family (grouped expert GEMM): FLOPs per launch / mean launch duration
+        prof = prof or {}
         gemm = {k: v for k, v in prof.items() if k.startswith("grouped_gemm") or k.startswith("grouped_wgrad") or k.startswith("dense_wgrad") or k == "gate_wgrad"
                 or k.startswith("dense_gemm")}
         detail = {}
@@ -524,12 +580,14 @@ def main():
                        "parallelism": "single GPU" if world == 1 else f"ep{world} (experts sharded, RCCL all-to-all)",
                        **({"ep_chunks": layer.chunks, "ep_direct": bool(a.ep_direct), "ep_chunks_trial_ms": ep_tune, "comm_world_size": dist.get_world_size(),
                            "comm_backend": "nccl (RCCL)"} if (world > 1 or a.force_ep) else {})},
-            "roofline": roof, "kernels": detail,
+            **({"roofline": roof, "kernels": detail} if a.full else {}),
             "peak_hbm_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
         }
         if roof is not None:
             roof["traffic"], roof["traffic_note"] = traffic_for(roof["kernel"], res["config"], a.dtype)
-        if world == 1 and not a.no_cpu_baseline:
+        if dumped is not None:
+            res["dump_outputs"] = dumped
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(a)
             except Exception as e:   # the GPU number stands even if the host cannot hold the CPU sample

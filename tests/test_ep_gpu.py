@@ -392,14 +392,14 @@ def test_pretrain_smoe_ep_equals_single_gpu(world, backend, dt_name, chunks, emp
 
 
 def test_bench_script_runs_small_config_and_ep_path():
-    """bench.py end to end on a small layer: the single-GPU path and (with --force-ep, world size 1 over RCCL) the exact code
+    """bench.py --full end to end on a small layer: the single-GPU path and (with --force-ep, world size 1 over RCCL) the exact code
     path the driver launches for N > 1.  One JSON line with the contract's keys."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     base = [sys.executable, os.path.join(root, "bench.py"), "--tokens", "2048", "--seq", "512", "--d-model", "256", "--d-ff", "512",
-            "--experts", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+            "--experts", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"]
     for extra in ([], ["--force-ep"], ["--force-ep", "--ep-chunks", "2"], ["--force-ep", "--ep-trial"]):
         env = dict(os.environ, MASTER_PORT=str(_free_port()))
         r = subprocess.run(base + extra, capture_output=True, text=True, timeout=600, env=env)
@@ -415,3 +415,39 @@ def test_bench_script_runs_small_config_and_ep_path():
         elif extra:
             assert ("ep_wait_exposed" if "--ep-chunks" in extra else "ep_all_to_all") in d["kernels"]
             assert d["config"]["ep_chunks"] == (2 if "--ep-chunks" in extra else 1)
+
+
+@pytest.mark.parametrize("extra", [[], ["--stack", "pretrain"], ["--graph"]])
+def test_bench_plain_run_and_dump_outputs(extra, tmp_path):
+    """A plain bench.py run (no --full) on a small layer: the headline keys, `--steps` timed steps, none of the --full figures;
+    --dump-outputs writes the last step's outputs and gradients as float32 .npy files under the 64 MB cap, the same arrays on a
+    second run with the same arguments."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--tokens", "2048", "--seq", "512", "--d-model", "256", "--d-ff", "512",
+            "--experts", "8", "--steps", "3", "--warmup", "1"] + extra
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run(base + ["--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        res = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in res, k
+        assert res["steps"] == 3 and res["value"] > 0 and res["ms_per_step"] > 0
+        assert not {"roofline", "kernels", "cpu_baseline"} & set(res)
+        files = sorted(os.listdir(d))
+        assert res["dump_outputs"]["files"] == len(files)
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 10 ** 6
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert "x_grad.npy" in arrays and any(f.startswith("grad.") for f in files)
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

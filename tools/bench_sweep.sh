@@ -1,7 +1,7 @@
 #!/bin/bash
 # Every bench workload once (regression sweep); one line per mode.  usage (GPU box, repo root): tools/bench_sweep.sh
 run() {
-  python bench.py "$@" --no-cpu-baseline 2>/dev/null | python -c "
+  python bench.py "$@" --full --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith(chr(123))][-1])
 g = d['roofline']['all_grouped_gemm'] if d.get('roofline') else {}

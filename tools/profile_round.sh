@@ -9,8 +9,8 @@ EXTRA="$*"          # extra bench.py flags (e.g. --dtype fp8 --experts 128 --sha
 ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
-CMD="python3 $ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline $EXTRA"
-python3 bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-5} --no-cpu-baseline $EXTRA > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || exit 1
+CMD="python3 $ROOT/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline $EXTRA"
+python3 bench.py --steps ${STEPS:-20} --warmup ${WARMUP:-5} --full --no-cpu-baseline $EXTRA > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || exit 1
 # ONLY_BENCH=1: just the bench line again (after traffic.json of THIS build has been collected into profiles/rNN/, so that the committed
 # line carries roofline.traffic instead of "collected on other kernel sources")
 [ -n "${ONLY_BENCH:-}" ] && exit 0
@@ -25,7 +25,7 @@ python3 tools/summarize_profile.py $(find $OUT/kt -name "*kernel_trace.csv") $OU
   --fetch $(find $OUT/pf -name "*counter_collection.csv") --write $(find $OUT/pw -name "*counter_collection.csv") \
   --mfma $(find $OUT/pm -name "*counter_collection.csv") \
   --traffic-json $OUT/traffic.json --workload $TAG --bench-json $OUT/bench_${TAG}_under_rocprof.json \
-  --title "round ${ROUND:-3}, build $TAG: rocprofv3 of \`python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline $EXTRA\` on MI355X" > /dev/null
+  --title "round ${ROUND:-3}, build $TAG: rocprofv3 of \`python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline $EXTRA\` on MI355X" > /dev/null
 cp $(find $OUT/kt -name "*kernel_stats.csv") $OUT/bench_${TAG}_kernel_stats.csv
 # the counter CSVs are large: keep the summaries only
 rm -rf $OUT/pf $OUT/pw $OUT/pm $OUT/kt/*/*kernel_trace.csv 2>/dev/null

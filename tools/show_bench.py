@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel table of a bench.py JSON line (mean launch ms x launches per step), largest first.  usage: show_bench.py <file>"""
+"""Per-kernel table of a `bench.py --full` JSON line (mean launch ms x launches per step), largest first.  usage: show_bench.py <file>"""
 import json
 import sys
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the per-kernel table of a bench.py JSON line (stdin): calls/step, ms/call, ms/step, rate."""
+"""Print the per-kernel table of a `bench.py --full` JSON line (stdin): calls/step, ms/call, ms/step, rate."""
 import json
 import sys
 
