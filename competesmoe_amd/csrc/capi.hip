@@ -47,6 +47,11 @@ int gg8f_rowspace(const void* Aq, int64_t lda, const void* As, int64_t ldas, con
                   int64_t ldb, int64_t ldbs, const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd,
                   void* C, void* C2, const void* aux, int64_t ldc, int epilogue, int act, const void* single_B,
                   const void* single_BS, const void* single_bias, hipStream_t st);
+int k_quantize_mxfp8_tokens(const void* x, int64_t ldx, const int32_t* offsets, int E, int C, int64_t n_pad, void* poff, void* q, void* s,
+                            void* qt, void* st, hipStream_t stream);
+int gg8f_wgrad(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Bq, int64_t ldb, const void* Bs, int64_t ldbs,
+               const int32_t* poff, int E, int Na, int Nb, void* const* c_ptrs, int64_t ldc, int out_dtype, int accumulate,
+               const int32_t* xcd_order, hipStream_t st);
 int k_router_select(const void*, int, int, int, int, int, int, float, float*, int32_t*, float*, hipStream_t);
 int k_router_select_bwd(const void*, int, int, int, int, int, int, float, const float*, const int32_t*, const float*, const float*,
                         const float*, void*, hipStream_t);
@@ -643,6 +648,47 @@ int csmoe_dense_gemm_mxfp8(const void* Aq, int64_t lda, const void* As, int64_t 
   if (int rc = fp8_shape_ok(lda, ldas, ldb, ldbs, ldc, N, Kd, Aq, C ? C : C2, "dense_gemm_mxfp8")) return rc;
   return gg8f_rowspace(Aq, lda, As, ldas, nullptr, nullptr, ldb, ldbs, nullptr, nullptr, 1, M, N, Kd, C, C2, aux, ldc, epilogue, act,
                        Bq, Bs, bias, (hipStream_t)stream);
+}
+
+
+int csmoe_quantize_mxfp8_tokens(const void* x, int64_t ldx, int n, int C, int dtype, const int32_t* offsets, int E, int64_t n_pad,
+                                int32_t* poff, void* qt, void* st, void* q, void* s, csmoe_stream_t stream) {
+  CSMOE_CHECK_ARG(dtype == CSMOE_BF16, "quantize_mxfp8_tokens: bad dtype %d (bf16 rows only)", dtype);
+  CSMOE_CHECK_ARG(E >= 1 && n >= 0 && C >= 0, "quantize_mxfp8_tokens: bad shape E=%d n=%d C=%d", E, n, C);
+  CSMOE_CHECK_ARG(offsets && poff, "quantize_mxfp8_tokens: null offsets / poff");
+  CSMOE_CHECK_ARG(!q == !s, "quantize_mxfp8_tokens: the row orientation needs both q and s");
+  CSMOE_CHECK_ARG(n_pad % 128 == 0 && n_pad >= csmoe_token_pad_bound(n, E),
+                  "quantize_mxfp8_tokens: n_pad %lld below the bound roundup(n + 127 E, 128) = %lld or not a multiple of 128",
+                  (long long)n_pad, (long long)csmoe_token_pad_bound(n, E));
+  CSMOE_CHECK_ARG(n_pad / 64 < 0x7fffffffll, "quantize_mxfp8_tokens: n_pad too large");
+  CSMOE_CHECK_ARG(C == 0 || (qt && st && (n == 0 || x)), "quantize_mxfp8_tokens: null pointer");
+  CSMOE_CHECK_ARG(ldx >= C, "quantize_mxfp8_tokens: leading dimension too small");
+  if (C % 32 != 0 || (ldx * 2) % 16 != 0 || ((uintptr_t)x & 15)) {
+    csmoe_set_error("quantize_mxfp8_tokens: needs C %% 32 == 0 and 16-byte aligned rows (C=%d ldx=%lld)", C, (long long)ldx);
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  return k_quantize_mxfp8_tokens(x, ldx, offsets, E, C, C == 0 ? 0 : n_pad, poff, q, s, qt, st, (hipStream_t)stream);
+}
+
+int64_t csmoe_token_pad_bound(int64_t n, int E) { return (n + 127 * (int64_t)E + 127) / 128 * 128; }
+
+int csmoe_grouped_wgrad_mxfp8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Bq, int64_t ldb, const void* Bs,
+                              int64_t ldbs, const int32_t* poff, int E, int64_t n_pad, int Na, int Nb, void* const* c_ptrs, int64_t ldc,
+                              int out_dtype, int accumulate, const int32_t* xcd_order, csmoe_stream_t stream) {
+  CSMOE_CHECK_ARG(out_dtype == CSMOE_F32 || out_dtype == CSMOE_BF16, "grouped_wgrad_mxfp8: bad out_dtype %d", out_dtype);
+  CSMOE_CHECK_ARG(E > 0 && Na > 0 && Nb > 0 && n_pad >= 0, "grouped_wgrad_mxfp8: bad shape E=%d Na=%d Nb=%d", E, Na, Nb);
+  CSMOE_CHECK_ARG(Na % 8 == 0 && Nb % 8 == 0, "grouped_wgrad_mxfp8: Na and Nb must be multiples of 8 (Na=%d Nb=%d)", Na, Nb);
+  CSMOE_CHECK_ARG(poff, "grouped_wgrad_mxfp8: null poff");
+  CSMOE_CHECK_ARG(c_ptrs && Aq && As && Bq && Bs, "grouped_wgrad_mxfp8: null pointer");
+  CSMOE_CHECK_ARG(n_pad % 128 == 0 && lda >= n_pad && ldb >= n_pad && ldas >= n_pad / 32 && ldbs >= n_pad / 32 && ldc >= Nb,
+                  "grouped_wgrad_mxfp8: n_pad must be a multiple of 128 and the leading dimensions at least n_pad (n_pad / 32 for scales)");
+  if (lda % 16 || ldb % 16 || ldas % 4 || ldbs % 4 || ldc % 8 || ((uintptr_t)Aq & 15) || ((uintptr_t)Bq & 15) || ((uintptr_t)As & 3) ||
+      ((uintptr_t)Bs & 3) || 256 * lda >= 0x80000000ll || 256 * ldb >= 0x80000000ll) {
+    csmoe_set_error("grouped_wgrad_mxfp8: needs 16-byte aligned operands, 4-byte aligned scales, ldc %% 8 == 0 and 256 rows under 2 GiB");
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  return gg8f_wgrad(Aq, lda, As, ldas, Bq, ldb, Bs, ldbs, poff, E, Na, Nb, c_ptrs, ldc, out_dtype, accumulate, xcd_order,
+                    (hipStream_t)stream);
 }
 
 

@@ -228,6 +228,119 @@ __global__ void __launch_bounds__(256) quant_both_kernel(const void* const* x_pt
   }
 }
 
+// ---- token-dim quantisation of binned rows (the operands of the MXFP8 weight gradient) ---------------------------------------
+// The weight gradient reduces over the tokens, so its operands need blocks of 32 consecutive BINNED ROWS OF ONE EXPERT: expert e's
+// count_e rows are laid out at padded positions poff[e] .. poff[e] + count_e, poff[e] = sum_{j<e} roundup(count_j, 128), the rest
+// of the expert's range up to poff[e+1] is zero.  Blocks start at the expert's first row, so none straddles two experts, and a
+// 128-byte K-tile of the GEMM belongs to one expert.
+
+// poff[0..E] from offsets[0..E]: one workgroup, a contiguous run of experts per thread and a scan over the 256 partial sums
+__global__ void __launch_bounds__(256) token_pad_offsets_kernel(const int32_t* offsets, int E, int32_t* poff) {
+  __shared__ int part[256];
+  const int t = threadIdx.x;
+  const int per = (E + 255) / 256;
+  const int e0 = min(E, t * per), e1 = min(E, e0 + per);
+  int sum = 0;
+  for (int e = e0; e < e1; ++e) sum += (offsets[e + 1] - offsets[e] + 127) & ~127;
+  part[t] = sum;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    const int add = t >= d ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  int run = part[t] - sum;                       // exclusive prefix
+  for (int e = e0; e < e1; ++e) {
+    poff[e] = run;
+    run += (offsets[e + 1] - offsets[e] + 127) & ~127;
+  }
+  if (t == 255) poff[E] = part[255];
+}
+
+// One 256-thread workgroup per 64 padded rows x 128 columns (quant_both_kernel's tile and unit mapping): the padded rows map to
+// binned source rows of ONE expert (its range is a multiple of 128 long), rows past the expert's count load as zeros.  Row output
+// (q / s, indexed by source row) for the real rows only, when requested; transposed output (qt / st) for all 64 padded rows.
+template <bool ROWS>
+__global__ void __launch_bounds__(256) quant_tokens_kernel(const bf16* x, int64_t ldx, const int32_t* offsets, const int32_t* poff,
+                                                           int E, int C, int64_t n_pad, uint8_t* q, uint8_t* s, uint8_t* qt,
+                                                           uint8_t* st) {
+  __shared__ __attribute__((aligned(16))) float tile[QB_R * QB_LD];
+  __shared__ int tile_e;
+  const int t = threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * QB_R;
+  const int c0 = blockIdx.y * QB_C;
+  if (r0 >= poff[E]) return;                     // past the last expert's range: not written
+  for (int j = t; j < E; j += 256)
+    if (poff[j] <= r0 && r0 < poff[j + 1]) tile_e = j;     // exactly one (non-empty) expert's range holds r0
+  __syncthreads();
+  const int e = tile_e;
+  const int64_t pos = r0 - poff[e];              // position of padded row r0 inside the expert's range
+  const int64_t src0 = offsets[e] + pos;         // its source row
+  const int64_t nreal = (int64_t)(offsets[e + 1] - offsets[e]) - pos;   // real rows from r0 on (may be <= 0)
+  const int nbc = C >> 5;
+  const int64_t nbr = n_pad >> 5;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int r = (t >> 5) + 8 * i, c = (t & 31) * 4;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (c0 + c < C && r < nreal) {
+      const bf16x4 h = *(const bf16x4*)(x + (src0 + r) * ldx + c0 + c);
+      v = f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+    }
+    *(f32x4*)(tile + r * QB_LD + c) = v;
+  }
+  __syncthreads();
+  if (ROWS) {
+    // ---- row-major output of the real rows: unit (row t / 4, column block t % 4)
+    const int r = t >> 2, bk = t & 3;
+    if (c0 + bk * 32 < C && r < nreal) {
+      float v[32];
+      float amax = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const f32x4 w4 = *(const f32x4*)(tile + r * QB_LD + bk * 32 + 4 * j);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { v[4 * j + k] = w4[k]; amax = fmaxf(amax, fabsf(w4[k])); }
+      }
+      const int sb = e8m0_of_amax(amax);
+      const float inv = inv_scale_of(sb);
+      u32x4 o0, o1;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        o0[j] = pack4_e4m3(v[4 * j] * inv, v[4 * j + 1] * inv, v[4 * j + 2] * inv, v[4 * j + 3] * inv);
+        o1[j] = pack4_e4m3(v[16 + 4 * j] * inv, v[17 + 4 * j] * inv, v[18 + 4 * j] * inv, v[19 + 4 * j] * inv);
+      }
+      uint8_t* dst = q + (src0 + r) * C + c0 + bk * 32;
+      *(u32x4*)dst = o0;
+      *(u32x4*)(dst + 16) = o1;
+      s[(src0 + r) * nbc + (c0 >> 5) + bk] = (uint8_t)sb;
+    }
+  }
+  {
+    // ---- transposed output: column t % 128, padded row block t / 128 (two threads complete a 64-byte run of the column)
+    const int c = t & 127, rbk = t >> 7;
+    if (c0 + c < C) {
+      float v[32];
+      float amax = 0.f;
+#pragma unroll
+      for (int i = 0; i < 32; ++i) { v[i] = tile[(rbk * 32 + i) * QB_LD + c]; amax = fmaxf(amax, fabsf(v[i])); }
+      const int sb = e8m0_of_amax(amax);
+      const float inv = inv_scale_of(sb);
+      u32x4 o0, o1;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        o0[j] = pack4_e4m3(v[4 * j] * inv, v[4 * j + 1] * inv, v[4 * j + 2] * inv, v[4 * j + 3] * inv);
+        o1[j] = pack4_e4m3(v[16 + 4 * j] * inv, v[17 + 4 * j] * inv, v[18 + 4 * j] * inv, v[19 + 4 * j] * inv);
+      }
+      uint8_t* dst = qt + (int64_t)(c0 + c) * n_pad + r0 + rbk * 32;
+      *(u32x4*)dst = o0;
+      *(u32x4*)(dst + 16) = o1;
+      st[(int64_t)(c0 + c) * nbr + (r0 >> 5) + rbk] = (uint8_t)sb;
+    }
+  }
+}
+
 }  // namespace
 
 int k_quantize_mxfp8_both(const void* const* x_ptrs, const void* x_single, int E, int64_t ldx, int R, int C, int in_dtype, void* q,
@@ -269,5 +382,21 @@ int k_quantize_mxfp8(const void* const* x_ptrs, const void* x_single, int E, int
       hipLaunchKernelGGL((quant_cols_kernel<float>), grid, block, 0, st, x_ptrs, (const float*)x_single, ldx, R, C, (uint8_t*)q, (uint8_t*)s, q_mat, s_mat);
   }
   CSMOE_CHECK_LAUNCH("quantize_mxfp8");
+  return CSMOE_OK;
+}
+
+int k_quantize_mxfp8_tokens(const void* x, int64_t ldx, const int32_t* offsets, int E, int C, int64_t n_pad, void* poff, void* q, void* s,
+                            void* qt, void* st, hipStream_t stream) {
+  hipLaunchKernelGGL(token_pad_offsets_kernel, dim3(1), dim3(256), 0, stream, offsets, E, (int32_t*)poff);
+  CSMOE_CHECK_LAUNCH("quantize_mxfp8_tokens (offsets)");
+  if (C <= 0 || n_pad <= 0) return CSMOE_OK;
+  dim3 grid((unsigned)(n_pad / QB_R), (unsigned)((C + QB_C - 1) / QB_C)), block(256);
+  if (q)
+    hipLaunchKernelGGL((quant_tokens_kernel<true>), grid, block, 0, stream, (const bf16*)x, ldx, offsets, (const int32_t*)poff, E, C,
+                       n_pad, (uint8_t*)q, (uint8_t*)s, (uint8_t*)qt, (uint8_t*)st);
+  else
+    hipLaunchKernelGGL((quant_tokens_kernel<false>), grid, block, 0, stream, (const bf16*)x, ldx, offsets, (const int32_t*)poff, E, C,
+                       n_pad, (uint8_t*)q, (uint8_t*)s, (uint8_t*)qt, (uint8_t*)st);
+  CSMOE_CHECK_LAUNCH("quantize_mxfp8_tokens");
   return CSMOE_OK;
 }

@@ -67,19 +67,6 @@ struct DmaW {
   unsigned vb_rl[2], vb_rh[2], vb_cl[2], vb_ch[2];
 };
 
-// Scalar (SMEM) load of 8 bytes from a wave-uniform address.  Written as asm because hipcc turns a plain load of the offsets /
-// pointer tables into a VECTOR load once the kernel also stores to global memory, and every use of such a load costs an
-// `s_waitcnt vmcnt(0)`: a wait for the prefetch DMA and for all earlier stores of the epilogue.  The tables are written before
-// the launch, so the scalar cache is coherent for them.
-__device__ __forceinline__ uint64_t sload_b64(const void* ptr) {
-  const uint64_t a = (uint64_t)ptr;
-  const uint64_t u = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
-                     (unsigned)__builtin_amdgcn_readfirstlane((int)a);
-  uint64_t r;
-  asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(u) : "memory");
-  return r;
-}
-
 // v = position in this workgroup's tile list.  Without p.xcd_order: the global tile order (expert-major).  With it: the tiles of
 // the experts dealt to this workgroup's XCD (csmoe_expert_order): entry [x * slots + k] = k-th expert of XCD x, heaviest first
 __device__ __forceinline__ TileW tile_of(const FastArgs& p, int v, int nct, int per_e) {

@@ -217,3 +217,270 @@ int gg8f_rowspace(const void* Aq, int64_t lda, const void* As, int64_t ldas, con
   CSMOE_CHECK_LAUNCH("grouped_gemm_mxfp8");
   return CSMOE_OK;
 }
+
+// ==================================================================================================== MXFP8 weight gradient
+// dW_e [Na, Nb] = sum_{k in [poff[e], poff[e+1])} At[:, k] Bt[:, k] for every expert e, both operands token-dim quantised by
+// csmoe_quantize_mxfp8_tokens: At [Na, n_pad] / Bt [Nb, n_pad] e4m3, contiguous along k, scales [., n_pad/32], every expert's k range
+// a multiple of 128 long and zero-padded, so that a K-tile never mixes two experts and the last one needs no masking.  An NT
+// product with a K range per tile, assembled from two kernels the project already has:
+//   * the K-loop, fragments, scale DMA and MFMA of gg8f_kernel above, unchanged (the A operand takes the place of the token rows,
+//     the B operand that of the weight rows; the operand and scale descriptors start at the expert's first k);
+//   * the persistent tile walk of gg8w_kernel (gemm_bf16_v2p.hip): one workgroup per CU walks its XCD's contiguous chunk of the
+//     expert-major tile order, or the experts dealt to its XCD (`xcd_order`), in bands of row tiles, and its store epilogue
+//     (fp32: one 1-KiB row segment per store instruction; bf16: 16-byte row pieces; non-temporal; optional accumulate).
+// Not carried over: gg8w's prefetch of the next tile's K-tile 0 during the epilogue (its staging tile would overlap this kernel's
+// scale slots); every tile starts with its own DMA prologue.
+namespace {
+
+struct Fp8WArgs {
+  const uint8_t* A; int64_t ld_a; const uint8_t* AS; int64_t ld_as;     // At [Na, *], scales [Na, */32]
+  const uint8_t* B; int64_t ld_b; const uint8_t* BS; int64_t ld_bs;     // Bt [Nb, *], scales [Nb, */32]
+  const int32_t* poff; int E; int NR, NC;
+  void* const* out_ptrs; int64_t ldc; int accumulate, out_f32;
+  const int32_t* xcd_order; int tile_band;
+};
+
+constexpr int CT8_LD = BN8 + 4;                  // fp32 staging row stride (floats): 64 rows x 1040 B
+static_assert(64 * CT8_LD * 4 <= LDS8_BYTES, "the staging tile overlays the operand images");
+
+__global__ void __launch_bounds__(512, 2) gg8wf_kernel(Fp8WArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int nct = (p.NC + BN8 - 1) / BN8;
+  const int nrt = (p.NR + BM8 - 1) / BM8;
+  const int per_e = nrt * nct;
+  const int total = per_e * p.E;
+  int v_begin, v_end, v_step;
+  if (p.xcd_order) {                             // experts dealt to the XCDs by row count (gg8w_kernel)
+    const int x = blockIdx.x & 7, slots = (p.E + 7) >> 3;
+    const int last_pos = ((slots - 1) & 1) ? 7 - x : x;
+    const int n_mine = slots - 1 + (8 * (slots - 1) + last_pos < p.E ? 1 : 0);
+    v_begin = blockIdx.x >> 3; v_end = n_mine * per_e; v_step = gridDim.x >> 3;
+  } else if ((gridDim.x & 7) == 0) {             // one contiguous chunk of the tile order per XCD
+    const int x = blockIdx.x & 7, q8 = total >> 3, r8 = total & 7;
+    const int cs = (x < r8) ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8;
+    v_begin = cs + (blockIdx.x >> 3); v_end = cs + q8 + (x < r8 ? 1 : 0); v_step = gridDim.x >> 3;
+  } else {
+    v_begin = blockIdx.x; v_end = total; v_step = gridDim.x;
+  }
+  const unsigned ldr_b = (unsigned)p.ld_a, ldc_b = (unsigned)p.ld_b;
+  const unsigned ldrs = (unsigned)p.ld_as, ldcs = (unsigned)p.ld_bs;
+
+  for (int v = v_begin; v < v_end; v += v_step) {
+    // thread-id derived values pinned inside the iteration (gg8w_kernel: left visible, hipcc hoists them across the loop and spills)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    __builtin_assume(tid >= 0 && tid < 512);
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 2, wn = wave & 3;
+
+    // ---------------- tile: expert, k range, output row / column tile ----------------
+    int e = v / per_e;
+    const int local = v - e * per_e;
+    if (p.xcd_order) e = (int)(unsigned)sload_b64(p.xcd_order + (blockIdx.x & 7) * ((p.E + 7) >> 3) + e);
+    const uint64_t oo = sload_b64(p.poff + e);    // poff[e], poff[e + 1]
+    const int k0 = __builtin_amdgcn_readfirstlane((int)(unsigned)oo);
+    const int kd = __builtin_amdgcn_readfirstlane((int)(unsigned)(oo >> 32) - k0);
+    e = __builtin_amdgcn_readfirstlane(e);
+    const int band = p.tile_band;
+    const int grp = local / (band * nct), rem = local - grp * band * nct;
+    const int g_eff = min(band, nrt - grp * band);
+    const int tr0 = __builtin_amdgcn_readfirstlane((grp * band + rem % g_eff) * BM8);
+    const int tc0 = __builtin_amdgcn_readfirstlane((rem / g_eff) * BN8);
+    const int rows = min(BM8, p.NR - tr0), ncols = min(BN8, p.NC - tc0);
+    const int red_len = kd >> 1;                 // in the DMA helpers' 2-byte units
+    const unsigned nsb = (unsigned)(kd >> 5);
+
+    __amdgpu_buffer_rsrc_t rs_r, rs_c, rs_rs, rs_cs;
+    unsigned vb_rl[2], vb_rh[2], vb_cl[2], vb_ch[2];
+    int ax_r[2], ax_c[2], ax_dummy[2];
+    rs_r = make_rsrc(p.A + (int64_t)tr0 * ldr_b + k0, (unsigned)rows * ldr_b);
+    dma_setup<KC, 2>(vb_rl, ax_r, ldr_b, 0, 0, 7, 0, 0, wave, lane);
+    dma_setup<KC, 2>(vb_rh, ax_dummy, ldr_b, 0, 0, 7, 0, 128, wave, lane);
+    rs_c = make_rsrc(p.B + (int64_t)tc0 * ldc_b + k0, (unsigned)ncols * ldc_b);
+    dma_setup<KC, 2>(vb_cl, ax_c, ldc_b, 0, 0, 7, 0, 0, wave, lane);
+    dma_setup<KC, 2>(vb_ch, ax_dummy, ldc_b, 0, 0, 7, 0, 128, wave, lane);
+    rs_rs = make_rsrc(p.AS + (int64_t)tr0 * ldrs + (k0 >> 5), (unsigned)rows * ldrs);
+    rs_cs = make_rsrc(p.BS + (int64_t)tc0 * ldcs + (k0 >> 5), (unsigned)ncols * ldcs);
+    const bool sc_rows = wave < 4;
+    const unsigned sc_vbase = (unsigned)((wave & 3) * 64 + lane) * (sc_rows ? ldrs : ldcs);
+
+    const int g = lane >> 4, i16 = lane & 15;
+    const int sw = (i16 >> 1) & 7;
+    const int f_lo = i16 * 128 + ((g ^ sw) << 4);
+    const int f_hi = i16 * 128 + (((g + 4) ^ sw) << 4);
+    const int r_blk0 = wm * 4, c_blk0 = wn * 2;
+
+    f32x4 acc[4][8];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int nk = kd >> 7;
+    const int rows_here = rows - wm * 64;
+    const int cols_here = ncols - wn * 32;
+    const bool rlo = rows_here > 0, rhi = rows_here > 128, clo = cols_here > 0, chi = cols_here > 128;
+
+    // ---------------- K-loop: gg8f_kernel's, hook for hook (SLOT / ISSUE_* / FRAG / MFMA8 as defined there) ----------------
+    if (rows <= 128) {
+      ISSUE_CL(0); ISSUE_CH(0); ISSUE_RL(0); ISSUE_SC(0); ISSUE_CL(1); ISSUE_CH(1); ISSUE_RL(1); ISSUE_SC(1);
+      WAIT_DMA(7);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+#define THIN_FRAG_DECL const char* sc = SCSLOT(s); i32x8 fc[4], fr[4]; int sc_c[4], sc_r[4];
+#define THIN_READ_CL(cb) fc[cb] = FRAG(i_cl, c_blk0 + cb); sc_c[cb] = *(const uint8_t*)(sc + 1024 + ((c_blk0 + cb) * 16 + i16) * 4 + g);
+#define THIN_READ_CH(cb) fc[2 + cb] = FRAG(i_ch, c_blk0 + cb); sc_c[2 + cb] = *(const uint8_t*)(sc + 1024 + (128 + (c_blk0 + cb) * 16 + i16) * 4 + g);
+#define THIN_READ_RL(rb) fr[rb] = FRAG(i_rl, r_blk0 + rb); sc_r[rb] = *(const uint8_t*)(sc + ((r_blk0 + rb) * 16 + i16) * 4 + g);
+#define THIN_KSTEPS 1
+#define THIN_MFMA(ks, cb, rb) MFMA8(acc[cb][rb], fc[cb], fr[rb], sc_c[cb], sc_r[rb]);
+#define THIN_ISSUE(s) ISSUE_CL(s + 2); ISSUE_CH(s + 2); ISSUE_RL(s + 2); ISSUE_SC(s + 2)
+#define THIN_WAIT(s) WAIT_DMA(7)
+#include "gemm_loop_thin.inc"
+    } else {
+      ISSUE_CL(0); ISSUE_CH(0); ISSUE_RL(0); ISSUE_SC(0); ISSUE_RH(0); ISSUE_CL(1); ISSUE_CH(1); ISSUE_RL(1); ISSUE_SC(1);
+      WAIT_DMA(9);
+      __builtin_amdgcn_s_barrier();
+      if (wm == 1) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+#define BAL_FRAG_DECL const char* sc = SCSLOT(s); i32x8 fc[4], fr[4]; int sc_c[4], sc_r[8];
+#define BAL_READ_CL(cb) fc[cb] = FRAG(i_cl, c_blk0 + cb); sc_c[cb] = *(const uint8_t*)(sc + 1024 + ((c_blk0 + cb) * 16 + i16) * 4 + g);
+#define BAL_READ_CH(cb) fc[2 + cb] = FRAG(i_ch, c_blk0 + cb); sc_c[2 + cb] = *(const uint8_t*)(sc + 1024 + (128 + (c_blk0 + cb) * 16 + i16) * 4 + g);
+#define BAL_READ_RL(rb) fr[rb] = FRAG(i_rl, r_blk0 + rb); sc_r[rb] = *(const uint8_t*)(sc + ((r_blk0 + rb) * 16 + i16) * 4 + g);
+#define BAL_READ_RH(rb) fr[rb] = FRAG(i_rh, r_blk0 + rb);
+#define BAL_PHASE_A_EXTRA                                                                                                      \
+  if (rhi && clo) {                                                                                                            \
+    _Pragma("unroll") for (int rb = 0; rb < 4; ++rb) sc_r[4 + rb] = *(const uint8_t*)(sc + (128 + (r_blk0 + rb) * 16 + i16) * 4 + g); \
+  }
+#define BAL_KSTEPS 1
+#define BAL_MFMA(ks, cb, rb, arb) MFMA8(acc[cb][arb], fc[cb], fr[rb], sc_c[cb], sc_r[arb]);
+#define BAL_ISSUE_A(s) ISSUE_RH(s + 1)
+#define BAL_ISSUE_B(s) ISSUE_CL(s + 2); ISSUE_CH(s + 2); ISSUE_RL(s + 2); ISSUE_SC(s + 2)
+#define BAL_WAIT_A(s) WAIT_DMA(9)
+#define BAL_WAIT_B(s) WAIT_DMA(9)
+#include "gemm_loop_bal.inc"
+      if (wm == 0) __builtin_amdgcn_s_barrier();
+    }
+    // the zero-fill DMAs of the K-tiles past the end may still be writing LDS: drain before the staging tile overlays the slots
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+
+    // ---------------- epilogue: four passes of 64 rows through an fp32 tile (gg8w_kernel's) ----------------
+    // pass (h, u): row blocks 4h + 2u + {0,1} of every wave -> staging row wm*32 + i*16 + (lane & 15)
+    //              = tile row h*128 + wm*64 + u*32 + i*16 + (lane & 15)
+    float* stg = (float*)smem;
+    typedef __attribute__((address_space(1))) char gchar;
+    typedef __attribute__((address_space(1))) f32x4 gf32x4;
+    typedef __attribute__((address_space(1))) bf16x8 gbf16x8;
+    gchar* Ce = (gchar*)(char*)sload_b64(p.out_ptrs + e);
+    const int nrows = p.NR - tr0;
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+      const int h = pass >> 1, u = pass & 1;
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int m = wm * 32 + i * 16 + i16;
+          const int n = (cb >> 1) * 128 + wn * 32 + (cb & 1) * 16 + 4 * g;
+          *(f32x4*)(stg + m * CT8_LD + n) = acc[cb][4 * h + 2 * u + i];
+        }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if (p.out_f32) {
+        // one store instruction = one 1-KiB row segment (64 lanes x 16 B)
+        const int ec4 = lane * 4, er8 = wave;
+        f32x4 rw[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) rw[j] = *(const f32x4*)(stg + (er8 + 8 * j) * CT8_LD + ec4);
+        if (tc0 + ec4 < p.NC) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const int r = er8 + 8 * j;
+            const int trow = h * 128 + (r >> 5) * 64 + u * 32 + (r & 31);
+            if (trow < nrows) {
+              gf32x4* dst = (gf32x4*)(Ce + ((int64_t)(tr0 + trow) * p.ldc + tc0 + ec4) * 4);
+              f32x4 a = rw[j];
+              if (p.accumulate) a += dst[0];
+              __builtin_nontemporal_store(a, dst);
+            }
+          }
+        }
+      } else {
+        // bf16: 8 columns (one 16-byte piece) of 4 rows per thread
+        const int ec = (tid & 31) * 8, er = tid >> 5;
+        f32x4 lo[4], hi[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          lo[j] = *(const f32x4*)(stg + (er + 16 * j) * CT8_LD + ec);
+          hi[j] = *(const f32x4*)(stg + (er + 16 * j) * CT8_LD + ec + 4);
+        }
+        if (tc0 + ec < p.NC) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int r = er + 16 * j;
+            const int trow = h * 128 + (r >> 5) * 64 + u * 32 + (r & 31);
+            if (trow < nrows) {
+              gbf16x8* dst = (gbf16x8*)(Ce + ((int64_t)(tr0 + trow) * p.ldc + tc0 + ec) * 2);
+              float vv[8] = {lo[j][0], lo[j][1], lo[j][2], lo[j][3], hi[j][0], hi[j][1], hi[j][2], hi[j][3]};
+              if (p.accumulate) {
+                const bf16x8 old = *dst;
+#pragma unroll
+                for (int t = 0; t < 8; ++t) vv[t] += (float)old[t];
+              }
+              bf16x8 o8;
+#pragma unroll
+              for (int t = 0; t < 8; ++t) o8[t] = (bf16)vv[t];
+              __builtin_nontemporal_store(o8, dst);
+            }
+          }
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // every thread's staging reads retired before the next pass / tile
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+    }
+  }   // persistent tile loop
+}
+
+int fp8w_grid(int64_t tiles) {
+  static int ncu = 0;
+  if (!ncu) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
+    if (ncu <= 0) ncu = 256;
+  }
+  return (int)std::min<int64_t>(tiles, ncu);
+}
+
+}  // namespace
+
+int gg8f_wgrad(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Bq, int64_t ldb, const void* Bs, int64_t ldbs,
+               const int32_t* poff, int E, int Na, int Nb, void* const* c_ptrs, int64_t ldc, int out_dtype, int accumulate,
+               const int32_t* xcd_order, hipStream_t st) {
+  Fp8WArgs p{};
+  p.A = (const uint8_t*)Aq; p.ld_a = lda; p.AS = (const uint8_t*)As; p.ld_as = ldas;
+  p.B = (const uint8_t*)Bq; p.ld_b = ldb; p.BS = (const uint8_t*)Bs; p.ld_bs = ldbs;
+  p.poff = poff; p.E = E; p.NR = Na; p.NC = Nb;
+  p.out_ptrs = c_ptrs; p.ldc = ldc; p.accumulate = accumulate; p.out_f32 = out_dtype == CSMOE_F32;
+  p.tile_band = E > 1 ? 5 : 4;                   // gg8_wgrad's band heights
+  const int64_t tiles = (int64_t)E * ((Na + BM8 - 1) / BM8) * ((Nb + BN8 - 1) / BN8);
+  if (tiles <= 0) return CSMOE_OK;
+  if (tiles > 0x7fffffff) { csmoe_set_error("grouped_wgrad_mxfp8: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
+  const int grid = fp8w_grid(tiles);
+  // dealing needs whole experts per XCD and a grid that is a multiple of 8 (gg8_wgrad)
+  const bool deal = xcd_order && (E % 8 == 0 || E >= 64) && grid % 8 == 0 && grid < tiles;
+  p.xcd_order = deal ? xcd_order : nullptr;
+  static bool done = false;
+  if (!done) {
+    hipError_t er = hipFuncSetAttribute((const void*)gg8wf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
+    if (er != hipSuccess) { csmoe_set_error("hipFuncSetAttribute: %s", hipGetErrorString(er)); return CSMOE_ERR_LAUNCH; }
+    done = true;
+  }
+  hipLaunchKernelGGL(gg8wf_kernel, dim3((unsigned)grid), dim3(512), LDS8_BYTES, st, p);
+  CSMOE_CHECK_LAUNCH("grouped_wgrad_mxfp8");
+  return CSMOE_OK;
+}

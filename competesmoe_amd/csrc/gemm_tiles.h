@@ -38,6 +38,19 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, un
 }
 
 
+// Scalar (SMEM) load of 8 bytes from a wave-uniform address (the persistent weight-gradient kernels' table reads).  Written as asm because hipcc turns a plain load of the offsets /
+// pointer tables into a VECTOR load once the kernel also stores to global memory, and every use of such a load costs an
+// `s_waitcnt vmcnt(0)`: a wait for the prefetch DMA and for all earlier stores of the epilogue.  The tables are written before
+// the launch, so the scalar cache is coherent for them.
+__device__ __forceinline__ uint64_t sload_b64(const void* ptr) {
+  const uint64_t a = (uint64_t)ptr;
+  const uint64_t u = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
+                     (unsigned)__builtin_amdgcn_readfirstlane((int)a);
+  uint64_t r;
+  asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(u) : "memory");
+  return r;
+}
+
 // ---- LDS-DMA fill of one 16 KiB tile image: NJ wave-instructions per wave (NJ * waves = 16) ----------------------
 // KC: tile rows are operand rows (stride ld_bytes), 64 reduction elements per row starting at red0.
 // KM: tile rows are 64 reduction rows, 128 operand columns starting at col0.

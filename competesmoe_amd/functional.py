@@ -1115,16 +1115,56 @@ def _quantize_weight_both(t: torch.Tensor, cache: bool):
     return out
 
 
+def _wgrad_fp8_out_dtype(pd):
+    return pd if pd in (torch.float32, torch.bfloat16) else torch.float32
+
+
+def _grouped_wgrad_fp8(at, ats, bt, bts, poff, bins, E: int, pd) -> torch.Tensor:
+    """_grouped_wgrad on the fp8 pipe: out[e] = at_e @ bt_e^T from token-dim quantised operands (ops.quantize_mxfp8_tokens).  Same
+    split-K policy: with too few output tiles for the chip every expert's padded range is cut into P chunks of whole 128-element
+    K-tiles (pseudo-experts, fp32 partials, one sum)."""
+    Na, Nb = at.shape[0], bt.shape[0]
+    od = _wgrad_fp8_out_dtype(pd)
+    tiles = E * ((Na + 255) // 256) * ((Nb + 255) // 256)
+    P = min(4, (640 + tiles - 1) // tiles, max(1, bins.n // (E * 1024)))
+    if not _WGRAD_SPLIT or tiles >= 512 or P < 2:
+        out = torch.empty(E, Na, Nb, dtype=od, device=at.device)
+        ops.grouped_wgrad_mxfp8(at, ats, bt, bts, poff, E, out, ops.ptr_table(out, E, Na * Nb * out.element_size()),
+                                xcd_order=bins.xcd_order)
+        return out if od == pd else out.to(pd)
+    chunk_off = ops.chunk_offsets(poff, E, P, 128)
+    part = torch.empty(E * P, Na, Nb, dtype=torch.float32, device=at.device)
+    ops.grouped_wgrad_mxfp8(at, ats, bt, bts, chunk_off, E * P, part, ops.ptr_table(part, E * P, Na * Nb * 4))
+    return ops.sum_partials(part.view(E * P, Na * Nb), E, P, pd).view(E, Na, Nb)
+
+
+def _dense_wgrad_fp8(at, ats, bt, bts, poff, M: int, out_dtype) -> torch.Tensor:
+    """_dense_wgrad on the fp8 pipe (E = 1), with its split-K policy: chunks of whole 128-element K-tiles as pseudo-experts."""
+    Na, Nb = at.shape[0], bt.shape[0]
+    tiles = ((Na + 255) // 256) * ((Nb + 255) // 256)
+    P = min(16, (512 + tiles - 1) // tiles, M // 1024)
+    if tiles >= 384 or P < 2:
+        od = _wgrad_fp8_out_dtype(out_dtype)
+        out = ops.dense_wgrad_mxfp8(at, ats, bt, bts, poff, out_dtype=od)
+        return out if od == out_dtype else out.to(out_dtype)
+    chunk_off = ops.chunk_offsets(poff, 1, P, 128)
+    part = torch.empty(P, Na, Nb, dtype=torch.float32, device=at.device)
+    ops.grouped_wgrad_mxfp8(at, ats, bt, bts, chunk_off, P, part, ops.ptr_table(part, P, Na * Nb * 4), tag="dense_wgrad_mxfp8_splitk")
+    return ops.dense_colsum(part.view(P, Na * Nb), out_dtype=out_dtype).view(Na, Nb)
+
+
 class MoEFFNPackedFP8(torch.autograd.Function):
     """MoEFFNPacked with the four row-space expert GEMMs of a step (GEMM 1, GEMM 2, dH, dXs) on the block-scaled fp8 matrix pipe
     (BASELINE config 5; `csmoe_grouped_gemm_mxfp8`): operands quantised to MXFP8 (e4m3 + one e8m0 scale per 32 elements along each
     GEMM's reduction dim), fp32 accumulation, bf16 results.  The weight gradients stay bf16 products of the bf16 activations
-    (`csmoe_grouped_wgrad`).  Master weights (fp32 or bf16) are quantised directly, once per use and orientation -- there is no
+    (`csmoe_grouped_wgrad`) unless `wgrad_fp8`: then they run on the fp8 pipe too (`csmoe_grouped_wgrad_mxfp8`), with the activations
+    and dy / dh quantised along the token dim inside every expert's rows (`csmoe_quantize_mxfp8_tokens`; dy and dh in the same pass
+    as their row orientation); everything else the backward returns is unchanged, bit for bit.  Master weights (fp32 or bf16) are quantised directly, once per use and orientation -- there is no
     bf16 operand copy -- or, with `cache`, once per parameter version (_quantize_weight_both).  No counterpart upstream (the
     reference has no fp8): checked against oracle/mxfp8.py, tests/test_fp8_gpu.py."""
 
     @staticmethod
-    def forward(ctx, x2, w, idx, keys, values, bias, act: int, combine_mode: int, cache: bool = False):
+    def forward(ctx, x2, w, idx, keys, values, bias, act: int, combine_mode: int, cache: bool = False, wgrad_fp8: bool = False):
         x2 = x2.contiguous()
         if x2.dtype != torch.bfloat16:
             raise ValueError("competesmoe_amd: the fp8 expert path takes bf16 activations (run under bf16 autocast)")
@@ -1150,6 +1190,7 @@ class MoEFFNPackedFP8(torch.autograd.Function):
         ctx.wq = (kq_b, ks_b, vq_b, vs_b)        # each master tensor is read ONCE per step: the backward's operands are kept
         ctx.w, ctx.keys, ctx.values = w, keys, values
         ctx.cfg = (act, None if bias is None else bias.dtype)
+        ctx.wgrad_fp8 = bool(wgrad_fp8)
         return out
 
     @staticmethod
@@ -1166,32 +1207,53 @@ class MoEFFNPackedFP8(torch.autograd.Function):
         dy, dw = ops.combine_bwd(dout.contiguous(), y if need_dw else None, bins, ctx.w, want_dw=need_dw, act_dtype=torch.bfloat16)
         kq, ks, vq, vs = ctx.wq
         ctx.wq = None
-        dyq, dys = ops.quantize_mxfp8(dy)
+        f8w = ctx.wgrad_fp8
+        if f8w and ctx.needs_input_grad[4]:
+            (dyt, dyts, poff), (dyq, dys) = ops.quantize_mxfp8_tokens(dy, bins.offsets, E, rows=True)
+        else:
+            dyq, dys = ops.quantize_mxfp8(dy)
         dh = ops.grouped_gemm_mxfp8(dyq, dys, vq, vs, bins.offsets, epilogue=L.EPI_ACTGRAD, act=act,                 # values as stored
                                     aux=hpre if hpre is not None else hact)
         del dyq, dys, vq, vs
         gk = gv = gb = None
         pd = keys.dtype
         if ctx.needs_input_grad[4]:
-            gv = _grouped_wgrad(hact, dy, bins, E, pd)                     # [E, F, Dout]
+            if f8w:
+                ht, hts, _ = ops.quantize_mxfp8_tokens(hact, bins.offsets, E)
+                gv = _grouped_wgrad_fp8(ht, hts, dyt, dyts, poff, bins, E, pd)     # [E, F, Dout]
+                del ht, hts, dyt, dyts
+            else:
+                gv = _grouped_wgrad(hact, dy, bins, E, pd)                 # [E, F, Dout]
+        dhq = dhs = None
         if ctx.needs_input_grad[3]:
-            gk = _grouped_wgrad(xs, dh, bins, E, pd)                       # [E, D, F]
+            if f8w:
+                xt, xts, poff = ops.quantize_mxfp8_tokens(xs, bins.offsets, E)
+                if ctx.needs_input_grad[0]:
+                    (dht, dhts, _), (dhq, dhs) = ops.quantize_mxfp8_tokens(dh, bins.offsets, E, rows=True)
+                else:
+                    dht, dhts, _ = ops.quantize_mxfp8_tokens(dh, bins.offsets, E)
+                gk = _grouped_wgrad_fp8(xt, xts, dht, dhts, poff, bins, E, pd)    # [E, D, F]
+                del xt, xts, dht, dhts
+            else:
+                gk = _grouped_wgrad(xs, dh, bins, E, pd)                   # [E, D, F]
         if bias_dtype is not None and ctx.needs_input_grad[5]:
             gb = _grouped_colsum(dh, bins.offsets, E, bias_dtype)
         dx2 = None
         if ctx.needs_input_grad[0]:
-            dhq, dhs = ops.quantize_mxfp8(dh)
+            if dhq is None:
+                dhq, dhs = ops.quantize_mxfp8(dh)
             dxs = ops.grouped_gemm_mxfp8(dhq, dhs, kq, ks, bins.offsets)   # keys as stored: dxs = dh @ keys[e]^T
             dx2 = ops.dispatch_rows_bwd(dxs, bins, T)
-        return dx2, dw, None, gk, gv, gb, None, None, None
+        return dx2, dw, None, gk, gv, gb, None, None, None, None
 
 
 class DenseFFNFP8(torch.autograd.Function):
     """The always-on shared expert on the same fp8 pipe: x [T, D] -> act(x @ w1 [D, Fs] (+ b1)) @ w2 [Fs, Dout] (packed layout of
-    the pretrain stack's `keys_shared[0]` / `values_shared[0]`, deepseekv2.py:97-105)."""
+    the pretrain stack's `keys_shared[0]` / `values_shared[0]`, deepseekv2.py:97-105).  `wgrad_fp8`: the weight gradients on the fp8
+    pipe as in MoEFFNPackedFP8 (one expert: E = 1)."""
 
     @staticmethod
-    def forward(ctx, x2, w1, b1, w2, act: int, cache: bool = False):
+    def forward(ctx, x2, w1, b1, w2, act: int, cache: bool = False, wgrad_fp8: bool = False):
         x2 = x2.contiguous()
         xq, xsc = ops.quantize_mxfp8(x2)
         (w1q_b, w1s_b), (w1q, w1s) = _quantize_weight_both(w1, cache)      # backward pair [D, Fs]; forward pair [Fs, D]
@@ -1203,6 +1265,7 @@ class DenseFFNFP8(torch.autograd.Function):
         y = ops.dense_gemm_mxfp8(hq, hs, w2q, w2s)
         ctx.save_for_backward(x2, hpre, hact, w1, w2, w1q_b, w1s_b, w2q_b, w2s_b)
         ctx.cfg = (act, None if b1 is None else b1.dtype)
+        ctx.wgrad_fp8 = bool(wgrad_fp8)
         return y
 
     @staticmethod
@@ -1210,16 +1273,39 @@ class DenseFFNFP8(torch.autograd.Function):
         x2, hpre, hact, w1, w2, w1q, w1s, w2q, w2s = ctx.saved_tensors
         act, b1_dtype = ctx.cfg
         dy = dy.contiguous()
-        dyq, dys = ops.quantize_mxfp8(dy)
+        f8w = ctx.wgrad_fp8
+        T = dy.shape[0]
+        if f8w and ctx.needs_input_grad[3]:
+            off = ops.dense_offsets(T, dy.device)
+            (dyt, dyts, poff), (dyq, dys) = ops.quantize_mxfp8_tokens(dy, off, 1, rows=True)
+        else:
+            dyq, dys = ops.quantize_mxfp8(dy)
         dh = ops.dense_gemm_mxfp8(dyq, dys, w2q, w2s, epilogue=L.EPI_ACTGRAD, act=act, aux=hpre if hpre is not None else hact)
         gw1 = gb1 = gw2 = dx = None
         if ctx.needs_input_grad[3]:
-            gw2 = _dense_wgrad(hact, dy, w2.dtype)                         # [Fs, Dout]
+            if f8w:
+                ht, hts, _ = ops.quantize_mxfp8_tokens(hact, off, 1)
+                gw2 = _dense_wgrad_fp8(ht, hts, dyt, dyts, poff, T, w2.dtype)     # [Fs, Dout]
+                del ht, hts, dyt, dyts
+            else:
+                gw2 = _dense_wgrad(hact, dy, w2.dtype)                     # [Fs, Dout]
+        dhq = dhs = None
         if ctx.needs_input_grad[1]:
-            gw1 = _dense_wgrad(x2, dh, w1.dtype)                           # [D, Fs]
+            if f8w:
+                off = ops.dense_offsets(T, dy.device)
+                xt, xts, poff = ops.quantize_mxfp8_tokens(x2, off, 1)
+                if ctx.needs_input_grad[0]:
+                    (dht, dhts, _), (dhq, dhs) = ops.quantize_mxfp8_tokens(dh, off, 1, rows=True)
+                else:
+                    dht, dhts, _ = ops.quantize_mxfp8_tokens(dh, off, 1)
+                gw1 = _dense_wgrad_fp8(xt, xts, dht, dhts, poff, T, w1.dtype)    # [D, Fs]
+                del xt, xts, dht, dhts
+            else:
+                gw1 = _dense_wgrad(x2, dh, w1.dtype)                       # [D, Fs]
         if b1_dtype is not None and ctx.needs_input_grad[2]:
             gb1 = _chunked_dense_colsum(dh, b1_dtype)
         if ctx.needs_input_grad[0]:
-            dhq, dhs = ops.quantize_mxfp8(dh)
+            if dhq is None:
+                dhq, dhs = ops.quantize_mxfp8(dh)
             dx = ops.dense_gemm_mxfp8(dhq, dhs, w1q, w1s)
-        return dx, gw1, gb1, gw2, None, None
+        return dx, gw1, gb1, gw2, None, None, None

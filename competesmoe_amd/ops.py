@@ -815,3 +815,65 @@ def dense_gemm_mxfp8(Aq: torch.Tensor, As: torch.Tensor, Bq: torch.Tensor, Bs: t
                                            _ptr(bias), M, N, Kd, _ptr(Cm), _ptr(C2), _ptr(aux), N, epilogue, act, _stream()),
                 "dense_gemm_mxfp8")
     return (Cm, C2) if want_c2 else Cm
+
+
+# ------------------------------------------------------------------------------------------------ MXFP8 weight gradients
+def token_pad_bound(n: int, E: int) -> int:
+    """Padded token length that holds every expert's rows rounded up to 128 (csmoe_token_pad_bound): known without the counts."""
+    return (n + 127 * E + 127) // 128 * 128
+
+
+def quantize_mxfp8_tokens(a: torch.Tensor, offsets: torch.Tensor, E: int, rows: bool = False):
+    """Binned rows a [n, C] (bf16) quantised along the TOKEN dim with blocks inside each expert's row range
+    (csmoe_quantize_mxfp8_tokens): returns (qt [C, n_pad], st [C, n_pad/32], poff [E+1] int32) and, with `rows`, also the row
+    orientation (q [n, C], s [n, C/32]) of the same pass -- bit-identical to quantize_mxfp8(a).  n_pad = token_pad_bound(n, E)."""
+    _need_cuda(a)
+    if a.stride(-1) != 1:
+        a = a.contiguous()
+    n, C = a.shape
+    n_pad = token_pad_bound(n, E)
+    dev = a.device
+    poff = torch.empty(E + 1, dtype=torch.int32, device=dev)
+    qt = torch.empty(C, n_pad, dtype=torch.uint8, device=dev)
+    st = torch.empty(C, n_pad // 32, dtype=torch.uint8, device=dev)
+    q = torch.empty(n, C, dtype=torch.uint8, device=dev) if rows else None
+    s = torch.empty(n, C // 32, dtype=torch.uint8, device=dev) if rows else None
+    with _timed("quantize_mxfp8_tokens" + ("_both" if rows else ""), n * C * (a.element_size() + 1 + int(rows))):
+        L.check(lib.csmoe_quantize_mxfp8_tokens(a.data_ptr(), a.stride(0), n, C, _dt(a), offsets.data_ptr(), E, n_pad,
+                                                poff.data_ptr(), qt.data_ptr(), st.data_ptr(), _ptr(q), _ptr(s), _stream()),
+                "quantize_mxfp8_tokens")
+    return ((qt, st, poff), (q, s)) if rows else (qt, st, poff)
+
+
+def grouped_wgrad_mxfp8(At: torch.Tensor, Ats: torch.Tensor, Bt: torch.Tensor, Bts: torch.Tensor, poff: torch.Tensor, E: int,
+                        out: torch.Tensor, out_ptrs: torch.Tensor, accumulate: bool = False, xcd_order: Optional[torch.Tensor] = None,
+                        tag: str = "grouped_wgrad_mxfp8"):
+    """out[e] = At[:, poff[e]:poff[e+1]] @ Bt[:, poff[e]:poff[e+1]]^T on the fp8 pipe (csmoe_grouped_wgrad_mxfp8); At [Na, n_pad] /
+    Bt [Nb, n_pad] with their scales from quantize_mxfp8_tokens; `out` is [E, Na, Nb] fp32 / bf16 (or any buffer the pointers index)."""
+    Na, n_pad = At.shape
+    Nb = Bt.shape[0]
+    with _timed(tag, 2.0 * Na * Nb * n_pad):
+        L.check(lib.csmoe_grouped_wgrad_mxfp8(At.data_ptr(), At.stride(0), Ats.data_ptr(), Ats.stride(0), Bt.data_ptr(), Bt.stride(0),
+                                              Bts.data_ptr(), Bts.stride(0), poff.data_ptr(), E, n_pad, Na, Nb, out_ptrs.data_ptr(),
+                                              Nb, _dt(out), int(accumulate), _ptr(xcd_order), _stream()), "grouped_wgrad_mxfp8")
+    return out
+
+
+_DENSE_POFF = {}
+
+
+def dense_offsets(n: int, device) -> torch.Tensor:
+    """offsets [0, n] of one dense expert (the row range handed to quantize_mxfp8_tokens), cached per (n, device)."""
+    key = (n, torch.device(device))
+    off = _DENSE_POFF.get(key)
+    if off is None:
+        off = _DENSE_POFF[key] = torch.tensor([0, n], dtype=torch.int32, device=device)
+    return off
+
+
+def dense_wgrad_mxfp8(At: torch.Tensor, Ats: torch.Tensor, Bt: torch.Tensor, Bts: torch.Tensor, poff: torch.Tensor,
+                      out_dtype=torch.float32) -> torch.Tensor:
+    """Dense form (E = 1) of grouped_wgrad_mxfp8: [Na, Nb] = At[:, 0:poff[1]] @ Bt[:, 0:poff[1]]^T."""
+    Na, Nb = At.shape[0], Bt.shape[0]
+    out = torch.empty(Na, Nb, dtype=out_dtype, device=At.device)
+    return grouped_wgrad_mxfp8(At, Ats, Bt, Bts, poff, 1, out, ptr_table(out, 1, 0), tag="dense_wgrad_mxfp8")

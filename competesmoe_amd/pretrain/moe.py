@@ -10,6 +10,7 @@ The MoE-attention branch (`is_att=True`, only used by `smoe_perturbed` upstream)
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional
 
 import torch
@@ -21,6 +22,9 @@ from .. import ops
 from ..functional import (DenseFFN, DenseFFNFP8, GateLogits, GateSelect, MoEFFNPacked, MoEFFNPackedFP8, MoEFFNPackedSlots, OperandFork,
                           RouterSelect)
 from .framework_layers import LoggingLayer, OncePerIterLayer, RegularizedLayer
+
+# default of args.fp8_wgrad, read once per process (CSMOE_FP8_WGRAD=1: the expert weight gradients on the fp8 pipe too)
+_FP8_WGRAD_ENV = os.environ.get("CSMOE_FP8_WGRAD", "0") == "1"
 
 
 def _act_code(fn) -> int:
@@ -88,6 +92,11 @@ class MoE(LoggingLayer, RegularizedLayer, OncePerIterLayer, nn.Module):
         self.fp8_experts = bool(getattr(args, "fp8_experts", False))
         # keep the quantised weights while the parameters are unchanged (micro-batches of one optimizer step): functional._FP8_WCACHE
         self.fp8_weight_cache = bool(getattr(args, "fp8_weight_cache", False))
+        # the expert weight gradients on the fp8 pipe too (token-dim quantised operands, csmoe_grouped_wgrad_mxfp8); default from
+        # CSMOE_FP8_WGRAD=1, off otherwise
+        self.fp8_wgrad = bool(getattr(args, "fp8_wgrad", _FP8_WGRAD_ENV))
+        if self.fp8_wgrad and not self.fp8_experts:
+            raise ValueError("competesmoe_amd: args.fp8_wgrad (or CSMOE_FP8_WGRAD=1) needs args.fp8_experts")
         self.selection_dropout = selection_dropout
         self.expert_dropout = expert_dropout
         self.sel_weight_scale = weight_scale
@@ -229,7 +238,7 @@ class MoE(LoggingLayer, RegularizedLayer, OncePerIterLayer, nn.Module):
             out = MoEFFNPackedFP8.apply(x2, wk.float().contiguous(), selected_experts.reshape(-1, K).int().contiguous(),
                                         self.keys if keys is None else keys, self.values if values is None else values,
                                         self.bias if bias is None else bias, self.act_code, L.COMBINE_DOT,
-                                        self.fp8_weight_cache and keys is None and values is None)
+                                        self.fp8_weight_cache and keys is None and values is None, self.fp8_wgrad)
             if res is not None:
                 out = res + out.view(res.shape)
             return out.view(*shp[:-1], -1)
@@ -260,7 +269,8 @@ class MoE(LoggingLayer, RegularizedLayer, OncePerIterLayer, nn.Module):
         op = op_dtype(x)
         b = None if bias_shared is None else bias_shared[0]
         if self.fp8_experts:
-            y = DenseFFNFP8.apply(self.operand(x), keys_shared[0], b, values_shared[0], self.act_code, self.fp8_weight_cache)
+            y = DenseFFNFP8.apply(self.operand(x), keys_shared[0], b, values_shared[0], self.act_code, self.fp8_weight_cache,
+                                  self.fp8_wgrad)
             return y.view(*shp[:-1], -1)
         y = DenseFFN.apply(self.operand(x), keys_shared[0], b, values_shared[0], None, self.act_code, L.B_KN)
         return y.view(*shp[:-1], -1)

@@ -370,6 +370,40 @@ int csmoe_dense_gemm_mxfp8(const void* Aq, int64_t lda, const void* As, int64_t 
                            int64_t ldbs, const void* bias, int M, int N, int Kd, void* C, void* C2, const void* aux, int64_t ldc,
                            int epilogue, int act, csmoe_stream_t stream);
 
+/* ---- MXFP8 weight gradients: operands quantised along the TOKEN dimension -------------------------------------------------
+ * Blocking contract.  A block is 32 consecutive BINNED rows of ONE expert.  Binned order is that of csmoe_bin_tokens (a stable
+ * counting sort: ascending t * K + k inside an expert -- the order `(idx == e).nonzero()` lists).  Expert e's count_e rows
+ * (count_e = offsets[e+1] - offsets[e]) occupy the padded positions poff[e] .. poff[e] + count_e - 1, with
+ *     poff[e] = sum_{j<e} roundup(count_j, 128),
+ * and the positions up to poff[e+1] hold zeros; blocks start at poff[e], so none mixes two experts, and every 128-element K-tile
+ * of the weight-gradient GEMM belongs to one expert (no masking).  The scale rule is that of csmoe_quantize_mxfp8; an all-zero
+ * padding block gets the zero-amax scale byte 0.
+ *
+ * csmoe_token_pad_bound: the padded length the host can size without reading the counts, roundup(n + 127 E, 128) >= poff[E].
+ *
+ * csmoe_quantize_mxfp8_tokens: binned rows x [n, C] bf16 (leading dim ldx, 16-byte aligned rows, C % 32 == 0) and the device
+ * offsets[E+1] of the experts' row ranges ->
+ *     poff [E+1] int32 (device),
+ *     qt [C, n_pad] e4m3 and st [C, n_pad/32] e8m0: column c of qt is column c of x in padded token order; positions from
+ *         poff[E] to n_pad are not written,
+ *     optionally (q and s non-null) the row orientation q [n, C] / s [n, C/32] of rows offsets[0] .. offsets[E] - 1 in the same pass,
+ *         bit-identical to csmoe_quantize_mxfp8 (transpose = 0) of those rows.
+ * n_pad % 128 == 0 and n_pad >= csmoe_token_pad_bound(n, E): no host round trip, the step stays capturable. */
+int64_t csmoe_token_pad_bound(int64_t n, int E);
+int csmoe_quantize_mxfp8_tokens(const void* x, int64_t ldx, int n, int C, int dtype, const int32_t* offsets, int E, int64_t n_pad,
+                                int32_t* poff, void* qt, void* st, void* q, void* s, csmoe_stream_t stream);
+/* Weight gradient on v_mfma_scale_f32_16x16x128_f8f6f4: for every expert e
+ *     C_e[0:Na, 0:Nb] = sum_{k in [poff[e], poff[e+1])} A[0:Na, k] B[0:Nb, k]
+ * with A = Aq [Na, n_pad] (lda) / As [Na, n_pad / 32] (ldas) and B = Bq [Nb, n_pad] (ldb) / Bs [Nb, n_pad / 32] (ldbs) from
+ * csmoe_quantize_mxfp8_tokens (poff ranges multiples of 128, inside [0, n_pad)).  E pseudo-experts may also be chunks of those
+ * ranges cut at multiples of 128 (csmoe_chunk_offsets of poff with align 128: split-K with fp32 partials).  c_ptrs[e] -> [Na, Nb]
+ * (leading dim ldc) in out_dtype CSMOE_F32 or CSMOE_BF16, `accumulate` != 0 adds into it, empty ranges give zeros; `xcd_order`
+ * (csmoe_expert_order, or null) deals the experts to the XCDs as in csmoe_grouped_wgrad.  The dense form is E = 1.
+ * Na % 8 == 0, Nb % 8 == 0, n_pad % 128 == 0, 16-byte aligned operands, lda / ldb >= n_pad, ldc % 8 == 0. */
+int csmoe_grouped_wgrad_mxfp8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Bq, int64_t ldb, const void* Bs,
+                              int64_t ldbs, const int32_t* poff, int E, int64_t n_pad, int Na, int Nb, void* const* c_ptrs, int64_t ldc,
+                              int out_dtype, int accumulate, const int32_t* xcd_order, csmoe_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
