@@ -24,6 +24,7 @@ COMBINE_SEQ, COMBINE_DOT, COMBINE_SEQ_RW = 0, 1, 2
 B_NK, B_KN = 0, 1
 EPI_PLAIN, EPI_BIAS, EPI_BIAS_ACT, EPI_ACTGRAD, EPI_ROUND_BIAS32_ACT, EPI_SOFTPLUS_ROWSUM, EPI_SOFTPLUS_GRAD = 0, 1, 2, 3, 4, 5, 6
 EPI_ACTGRAD_ROWSCALE = 7
+EPI_ACCUM = 8                 # C = round(C + round(A @ B)): csmoe_dense_gemm only (include/csmoe.h)
 
 ACT_CODES = {"none": ACT_NONE, "relu": ACT_RELU, "gelu": ACT_GELU, "gelu_tanh": ACT_GELU_TANH, "silu": ACT_SILU,
              "quick_gelu": ACT_QUICK_GELU}

@@ -142,6 +142,11 @@ static rowspace_fn pick_rowspace(int M, int N, int Kd, int b_layout, int kernel)
   if (!big) return gg_fast_rowspace;
   return use_v4_rowspace(Kd, b_layout, kernel) ? gg4_rowspace : gg8_rowspace;
 }
+// CSMOE_EPI_ACCUM outside csmoe_dense_gemm: refused before anything is launched, so C is never half-written
+static int accum_unsupported(const char* what) {
+  csmoe_set_error("%s: CSMOE_EPI_ACCUM is a csmoe_dense_gemm epilogue only", what);
+  return CSMOE_ERR_UNSUPPORTED;
+}
 static bool use_v2_wgrad(int M, int Na, int Nb) {
   int p = gemm_pref();
   if (p == 1) return false;
@@ -300,6 +305,7 @@ int csmoe_grouped_gemm(const void* A, int64_t lda, const void* const* b_ptrs, in
                        const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2,
                        const void* aux, int64_t ldc, int epilogue, int act, int dtype, int kernel,
                        csmoe_stream_t stream) {
+  if (epilogue == CSMOE_EPI_ACCUM) return accum_unsupported("grouped_gemm");
   CSMOE_CHECK_ARG(dtype_ok(dtype), "grouped_gemm: bad dtype %d", dtype);
   CSMOE_CHECK_ARG(E > 0 && M >= 0 && N > 0 && Kd > 0, "grouped_gemm: bad shape E=%d M=%d N=%d Kd=%d", E, M, N, Kd);
   CSMOE_CHECK_ARG(b_layout == CSMOE_B_NK || b_layout == CSMOE_B_KN, "grouped_gemm: bad B layout %d", b_layout);
@@ -343,6 +349,8 @@ int csmoe_dense_gemm(const void* A, int64_t lda, const void* B, int b_layout, in
   CSMOE_CHECK_ARG(dtype_ok(dtype) && M >= 0 && N > 0 && Kd > 0, "dense_gemm: bad arguments");
   CSMOE_CHECK_ARG(M == 0 || (A && B && (C || ((epilogue == CSMOE_EPI_BIAS_ACT || epilogue == CSMOE_EPI_ROUND_BIAS32_ACT) && C2))), "dense_gemm: null pointer");
   CSMOE_CHECK_ARG(M == 0 || epilogue != CSMOE_EPI_ACTGRAD || aux, "dense_gemm: ACTGRAD epilogue needs aux");
+  CSMOE_CHECK_ARG(epilogue != CSMOE_EPI_ACCUM || (!bias && !C2 && !aux && ldc >= N && (M == 0 || C)),
+                  "dense_gemm: ACCUM adds the product into C (ldc >= N) and takes no bias / C2 / aux");
   if (M == 0) return CSMOE_OK;
   hipStream_t st = (hipStream_t)stream;
   if (epilogue == CSMOE_EPI_SOFTPLUS_ROWSUM || epilogue == CSMOE_EPI_SOFTPLUS_GRAD) {
@@ -626,6 +634,7 @@ int csmoe_grouped_gemm_mxfp8(const void* Aq, int64_t lda, const void* As, int64_
                              const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2, const void* aux, int64_t ldc,
                              int epilogue, int act, csmoe_stream_t stream) {
   CSMOE_CHECK_ARG(E > 0 && M >= 0 && N > 0 && Kd > 0, "grouped_gemm_mxfp8: bad shape E=%d M=%d N=%d Kd=%d", E, M, N, Kd);
+  if (epilogue == CSMOE_EPI_ACCUM) return accum_unsupported("grouped_gemm_mxfp8");
   CSMOE_CHECK_ARG(epilogue >= 0 && epilogue <= 3 && act >= 0 && act <= 5, "grouped_gemm_mxfp8: bad epilogue/act");
   CSMOE_CHECK_ARG(bq_ptrs && bs_ptrs && offsets && (M == 0 || (Aq && As && (C || (epilogue == CSMOE_EPI_BIAS_ACT && C2)))),
                   "grouped_gemm_mxfp8: null pointer");
@@ -641,6 +650,7 @@ int csmoe_dense_gemm_mxfp8(const void* Aq, int64_t lda, const void* As, int64_t 
                            int64_t ldbs, const void* bias, int M, int N, int Kd, void* C, void* C2, const void* aux, int64_t ldc,
                            int epilogue, int act, csmoe_stream_t stream) {
   CSMOE_CHECK_ARG(M >= 0 && N > 0 && Kd > 0, "dense_gemm_mxfp8: bad shape");
+  if (epilogue == CSMOE_EPI_ACCUM) return accum_unsupported("dense_gemm_mxfp8");
   CSMOE_CHECK_ARG(epilogue >= 0 && epilogue <= 3 && act >= 0 && act <= 5, "dense_gemm_mxfp8: bad epilogue/act");
   CSMOE_CHECK_ARG(M == 0 || (Aq && As && Bq && Bs && (C || (epilogue == CSMOE_EPI_BIAS_ACT && C2))), "dense_gemm_mxfp8: null pointer");
   CSMOE_CHECK_ARG(M == 0 || epilogue != CSMOE_EPI_ACTGRAD || aux, "dense_gemm_mxfp8: ACTGRAD epilogue needs aux");
@@ -697,6 +707,7 @@ int csmoe_grouped_gemm_f32w(const void* A, int64_t lda, const void* const* b_ptr
                             const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2,
                             const void* aux, int64_t ldc, int epilogue, int act, csmoe_stream_t stream) {
   CSMOE_CHECK_ARG(E > 0 && M >= 0 && N > 0 && Kd > 0, "grouped_gemm_f32w: bad shape E=%d M=%d N=%d Kd=%d", E, M, N, Kd);
+  if (epilogue == CSMOE_EPI_ACCUM) return accum_unsupported("grouped_gemm_f32w");
   CSMOE_CHECK_ARG(epilogue >= 0 && epilogue <= 4 && act >= 0 && act <= 5, "grouped_gemm_f32w: bad epilogue/act");
   CSMOE_CHECK_ARG(b_ptrs && offsets && (M == 0 || (A && (C || ((epilogue == CSMOE_EPI_BIAS_ACT || epilogue == CSMOE_EPI_ROUND_BIAS32_ACT) && C2)))),
                   "grouped_gemm_f32w: null pointer");

@@ -183,7 +183,12 @@ __global__ void __launch_bounds__(256, 2) gg_fast_kernel(FastArgs p) {
       float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       const int64_t o = (int64_t)(row0 + r) * p.ldc + ncol;
       bf16x8 o0;
-      if (p.epilogue == CSMOE_EPI_ACTGRAD || p.epilogue == CSMOE_EPI_ACTGRAD_ROWSCALE) {
+      if (p.epilogue == CSMOE_EPI_ACCUM) {      // C = round(C + round(acc)): torch's bf16 add_ of the rounded product
+        const bf16x8 c8 = *(const bf16x8*)((const bf16*)p.C + o);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o0[j] = (bf16)((float)c8[j] + (float)(bf16)v[j]);
+        *(bf16x8*)((bf16*)p.C + o) = o0;
+      } else if (p.epilogue == CSMOE_EPI_ACTGRAD || p.epilogue == CSMOE_EPI_ACTGRAD_ROWSCALE) {
         const bf16x8 h8 = *(const bf16x8*)((const bf16*)p.aux + o);
         float h[8];
 #pragma unroll

@@ -60,7 +60,7 @@ __device__ unsigned long long* g_stamp_buf = nullptr;
 #define RT_STAMP(var) do { } while (0)
 #endif
 
-template <int ROWK, int COLK, int MODE, int SCHED>
+template <int ROWK, int COLK, int MODE, int SCHED, bool ACC = false>   // ACC: the CSMOE_EPI_ACCUM epilogue only (rowspace_epilogue)
 __global__ void __launch_bounds__(512, 2) gg8_kernel(FastArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   RT_STAMP(st_entry);
@@ -279,7 +279,8 @@ __global__ void __launch_bounds__(512, 2) gg8_kernel(FastArgs p) {
   // ---------------- epilogue ----------------
   if constexpr (MODE == 0) {
     const EpiArgs ea{p.C, p.C2, p.aux, p.bias_ptrs ? p.bias_ptrs[e] : p.single_bias, p.ldc, p.epilogue, p.act, p.NC};
-    rowspace_epilogue(ea, acc, smem, row0, rows, tc0, wm, wn, lane);
+    if constexpr (ACC) epi_run<EC_ACCUM, 0>(ea, acc, smem, row0, rows, tc0, wm, wn, lane);
+    else rowspace_epilogue(ea, acc, smem, row0, rows, tc0, wm, wn, lane);
   } else {
     // weight-gradient form (kept for the MODE = 1 instantiation; the launched weight-gradient kernel is gemm_bf16_v2p.hip's):
     // two passes of 128 rows through an fp32 LDS tile
@@ -413,7 +414,15 @@ static int rowspace_launch(const void* A, int64_t lda, const void* const* b_ptrs
       hipLaunchKernelGGL((gg8_kernel<KC, KM, 0, S>), dim3((unsigned)grid), dim3(512), LDS2_BYTES, st, p);             \
     }                                                                                                                 \
   } while (0)
-  if (sp == BAL) LAUNCH_SCHED(BAL); else LAUNCH_SCHED(WIDE);
+  if (epilogue == CSMOE_EPI_ACCUM) {      // each layout with its default schedule (sched_pref without CSMOE_GEMM_SCHED)
+    if (b_layout == CSMOE_B_NK) {
+      if ((rc = set_lds2(gg8_kernel<KC, KC, 0, BAL, true>))) return rc;
+      hipLaunchKernelGGL((gg8_kernel<KC, KC, 0, BAL, true>), dim3((unsigned)grid), dim3(512), LDS2_BYTES, st, p);
+    } else {
+      if ((rc = set_lds2(gg8_kernel<KC, KM, 0, WIDE, true>))) return rc;
+      hipLaunchKernelGGL((gg8_kernel<KC, KM, 0, WIDE, true>), dim3((unsigned)grid), dim3(512), LDS2_BYTES, st, p);
+    }
+  } else if (sp == BAL) LAUNCH_SCHED(BAL); else LAUNCH_SCHED(WIDE);
   CSMOE_CHECK_LAUNCH("grouped_gemm(bf16 v2)");
   return CSMOE_OK;
 }

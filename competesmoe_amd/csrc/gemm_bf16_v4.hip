@@ -199,7 +199,7 @@ __device__ __forceinline__ void k_loop(f32x4 (&acc)[8][8], LoopState& st, int nk
   }
 }
 
-template <int COLK>
+template <int COLK, bool ACC = false>      // ACC: the CSMOE_EPI_ACCUM epilogue only (gemm_epilogue.h, rowspace_epilogue)
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) gg4_kernel(FastArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
@@ -292,7 +292,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 #ifdef CSMOE_V4_DEV      // tools/v4_tune.sh: the plain epilogue only (seconds instead of minutes to compile)
   epi_run<EC_PLAIN, 0, Lay4>(ea, acc, smem, row0, rows, tc0, wm, wn, lane);
 #else
-  rowspace_epilogue<Lay4>(ea, acc, smem, row0, rows, tc0, wm, wn, lane);
+  if constexpr (ACC) epi_run<EC_ACCUM, 0, Lay4>(ea, acc, smem, row0, rows, tc0, wm, wn, lane);
+  else rowspace_epilogue<Lay4>(ea, acc, smem, row0, rows, tc0, wm, wn, lane);
 #endif
 }
 
@@ -326,7 +327,10 @@ int gg4_rowspace(const void* A, int64_t lda, const void* const* b_ptrs, int b_la
   if (grid <= 0) return CSMOE_OK;
   if (grid > 0x7fffffff) { csmoe_set_error("grouped_gemm: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
   int rc;
-  if (b_layout == CSMOE_B_NK) {
+  if (epilogue == CSMOE_EPI_ACCUM) {      // K-contiguous weights only (gg4_rowspace_ok)
+    if ((rc = set_lds4(gg4_kernel<KC, true>))) return rc;
+    hipLaunchKernelGGL((gg4_kernel<KC, true>), dim3((unsigned)grid), dim3(256), LDS4_BYTES, st, p);
+  } else if (b_layout == CSMOE_B_NK) {
     if ((rc = set_lds4(gg4_kernel<KC>))) return rc;
     hipLaunchKernelGGL((gg4_kernel<KC>), dim3((unsigned)grid), dim3(256), LDS4_BYTES, st, p);
   } else {

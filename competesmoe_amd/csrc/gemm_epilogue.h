@@ -11,7 +11,9 @@
 //     every variant of the interface applies its activation to the ROUNDED product, so nothing is lost by rounding first;
 //   * is instantiated per (variant, activation) with the choice made once per tile, so each row loop is straight-line code;
 //   * walks 16 rows per thread fully unrolled (row = t/32 + 16 i, 8 columns per thread: 512-byte row segments per half wave);
-//   * fetches the saved pre-activations of the activation-gradient variant before the staging, 16 loads in flight per thread.
+//   * fetches the saved pre-activations of the activation-gradient variant before the staging, 16 loads in flight per thread;
+//     the accumulating variant (CSMOE_EPI_ACCUM) fetches the tile's current C rows the same way, so their latency hides under the
+//     staging and the add is one fp32 add + round per element on the way out (C is read and written by the same thread only).
 #pragma once
 #include "gemm_tiles.h"
 
@@ -40,7 +42,8 @@ struct Lay4 {
   static __device__ __forceinline__ int n(int wn, int cb, int g) { return wn * 128 + cb * 16 + 4 * g; }
 };
 
-enum { EC_PLAIN = 0, EC_BIAS = 1, EC_BIAS_ACT = 2, EC_R32_ACT = 3, EC_ACTGRAD = 4, EC_ACTGRAD_RS = 5 };   // _RS: + per-row scale (C2 slot)
+enum { EC_PLAIN = 0, EC_BIAS = 1, EC_BIAS_ACT = 2, EC_R32_ACT = 3, EC_ACTGRAD = 4, EC_ACTGRAD_RS = 5,   // _RS: + per-row scale (C2 slot)
+       EC_ACCUM = 6 };                                                                             // C = round(C + round(acc))
 constexpr int ACT_RT = -1;                          // activation chosen at run time (the rarer ones share one instantiation)
 
 template <int ACT>
@@ -67,15 +70,16 @@ __device__ __forceinline__ void epi_run(const EpiArgs& p, const f32x4 (&acc)[LAY
   // rows go through in chunks of 16 per thread (one chunk for the 512-thread layout, two for the 256-thread one: a 32-row
   // straight-line body times the 12 (variant, activation) instantiations was 1.3 MB of code and minutes of compile time)
   constexpr int CH = 16, NCH = RPT / CH;
-  bf16x8 hq[CH], hq_next[CH];
+  bf16x8 hq[CH], hq_next[CH];                  // EC_ACTGRAD*: the saved pre-activations; EC_ACCUM: the current C rows
   float rs[CH], rs_next[CH];                   // EC_ACTGRAD_RS: this thread's row scales, fetched with the pre-activations
   auto fetch_aux = [&](int h, bf16x8 (&q)[CH], float (&sc)[CH]) {
-    if constexpr (CLS == EC_ACTGRAD || CLS == EC_ACTGRAD_RS) {
+    if constexpr (CLS == EC_ACTGRAD || CLS == EC_ACTGRAD_RS || CLS == EC_ACCUM) {
+      const bf16* src = CLS == EC_ACCUM ? (const bf16*)p.C : (const bf16*)p.aux;
       if (col_ok) {
 #pragma unroll
         for (int i = 0; i < CH; ++i) {
           const int r = er + RSTEP * (h * CH + i);
-          if (r < rows) q[i] = *(const bf16x8*)((const bf16*)p.aux + (int64_t)(row0 + r) * p.ldc + ncol);
+          if (r < rows) q[i] = *(const bf16x8*)(src + (int64_t)(row0 + r) * p.ldc + ncol);
         }
       }
     }
@@ -148,6 +152,11 @@ __device__ __forceinline__ void epi_run(const EpiArgs& p, const f32x4 (&acc)[LAY
       const int64_t o = (int64_t)(row0 + r) * p.ldc + ncol;
       if constexpr (CLS == EC_PLAIN || CLS == EC_BIAS) {
         *(bf16x8*)((bf16*)p.C + o) = o0;
+      } else if constexpr (CLS == EC_ACCUM) {      // torch's bf16 add_: both addends widened, one rounding
+        bf16x8 o1;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o1[j] = (bf16)((float)hq[i][j] + (float)o0[j]);
+        *(bf16x8*)((bf16*)p.C + o) = o1;
       } else if constexpr (CLS == EC_ACTGRAD || CLS == EC_ACTGRAD_RS) {
         float h[8];
 #pragma unroll
@@ -273,6 +282,9 @@ __device__ __forceinline__ void epi_by_act(const EpiArgs& p, const f32x4 (&acc)[
 }
 
 // Called by all of the workgroup's threads after the K-loop's LDS traffic has drained (the staging tile overlays the operand images).
+// CSMOE_EPI_ACCUM is not a case here: the kernels that take it (gemm_bf16_v2.hip, gemm_bf16_v4.hip) run epi_run<EC_ACCUM> in an
+// instantiation of their own, so the register allocation and code of the instantiations every other launch uses stay as they were
+// (one more case in this switch cost the step 1 % through the K-loop's code).
 template <typename LAY = Lay8>
 __device__ __forceinline__ void rowspace_epilogue(const EpiArgs& p, const f32x4 (&acc)[LAY::NCB][LAY::NRB], char* smem, int row0, int rows,
                                                   int tc0, int wm, int wn, int lane) {

@@ -116,7 +116,9 @@ __global__ void __launch_bounds__(256) gg_generic_kernel(GGArgs p) {
       if (row >= r_lim) continue;
       int64_t o = (int64_t)(tile_r0 + row) * p.ldc + n;
       float v = acc[r];
-      if (p.epilogue == CSMOE_EPI_ACTGRAD || p.epilogue == CSMOE_EPI_ACTGRAD_ROWSCALE) {
+      if (p.epilogue == CSMOE_EPI_ACCUM) {        // bf16: round(C + round(acc)); fp32: C + acc
+        DT<T>::st((T*)p.C + o, DT<T>::ld((const T*)p.C + o) + DT<T>::rnd(v));
+      } else if (p.epilogue == CSMOE_EPI_ACTGRAD || p.epilogue == CSMOE_EPI_ACTGRAD_ROWSCALE) {
         float g = DT<T>::rnd(v);
         if (p.epilogue == CSMOE_EPI_ACTGRAD_ROWSCALE) g = DT<T>::rnd(((const float*)p.C2)[tile_r0 + row] * g);
         float h = DT<T>::ld((const T*)p.aux + o);

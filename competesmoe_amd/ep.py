@@ -613,6 +613,13 @@ class EPFFNPacked(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        return EPFFNPacked._backward(ctx, dout)
+
+    @staticmethod
+    def _backward(ctx, dout, dy_extra=None):
+        """`dy_extra`: gradient of the per-slot outputs (EPFFNPackedSlots) in binned order, operand dtype.  It travels to the owners as
+        one more message per lane and enters there as functional._ffn_backward's `dy_extra` does: its own dH product (W2^T and the
+        activation gradient, no routing weight) added to dH, and added to dy for d values; it carries no d w."""
         from . import functional as Fn
         if ctx.saved is None:
             raise RuntimeError("competesmoe_amd: saved activations were freed by the first backward pass; a second backward "
@@ -638,6 +645,7 @@ class EPFFNPacked(torch.autograd.Function):
             sent = [(ln.send(rows_out), ln.send(w_out)) for ln in lanes]
         else:
             sent = [(ln.send(dy), None) for ln in lanes]
+        extra_sent = [ln.send(dy_extra) for ln in lanes] if dy_extra is not None else [None] * len(lanes)
         gk = gv = gb = None
         if need_params:
             es = torch.tensor([], dtype=pd).element_size()
@@ -649,14 +657,17 @@ class EPFFNPacked(torch.autograd.Function):
         dxs = torch.empty(bins.n, D, dtype=op, device=dev) if need_dx else None
         dots = torch.empty(bins.n, 1, dtype=torch.float32, device=dev) if use_dot else None
         back = []
-        for ln, (rows_s, w_s), (rs, hpre, hact) in zip(lanes, sent, saved):
+        for ln, (rows_s, w_s), ex_s, (rs, hpre, hact) in zip(lanes, sent, extra_sent, saved):
             with ops._timed("ep_wait_exposed"):
                 rows_s[1].wait()
                 if w_s is not None:
                     w_s[1].wait()
+                if ex_s is not None:
+                    ex_s[1].wait()
             e0, e1 = ln.cp.e0, ln.cp.e1
             Ec, lb = e1 - e0, ln.lb
             dys = ln.arrived(rows_s[0])
+            ex = None if ex_s is None else ln.arrived(ex_s[0])
             aux = hpre if hpre is not None else hact
             if scale_after:
                 wr = ln.arrived(w_s[0]).view(-1)
@@ -671,9 +682,16 @@ class EPFFNPacked(torch.autograd.Function):
                 if use_dot:
                     col = ops.finish_row_dot(dot).view(-1, 1) if dot is not None else torch.empty(0, 1, dtype=torch.float32, device=dev)
                     back.append(ln.give_back(col, dots))
+                if ex is not None:                       # the unweighted per-slot rows: their own product, added to dH
+                    dh = dh + ops.grouped_gemm(ex.contiguous(), tab.w2_ptrs[e0:e1], L.B_NK, Dout, F, lb.offsets, Ec, epilogue=L.EPI_ACTGRAD,
+                                               act=tab.act, aux=aux)
                 if need_params:                          # dy = round(w * upstream row), what combine_bwd hands the single-GPU d values
                     dys = ops.scale_rows(dys, wr)
+                    if ex is not None:
+                        dys = dys + ex
             else:
+                if ex is not None:                       # dy + extra through one dH product, as the single-GPU backward forms it
+                    dys = dys + ex
                 dh = ops.grouped_gemm(dys, tab.w2_ptrs[e0:e1], L.B_NK, Dout, F, lb.offsets, Ec, epilogue=L.EPI_ACTGRAD, act=tab.act, aux=aux)
             if need_dx:                                  # input gradient first: its return trip overlaps this group's weight gradients
                 back.append(ln.give_back(ops.grouped_gemm(dh, tab.w1_ptrs[e0:e1], L.B_NK, F, D, lb.offsets, Ec), dxs))
@@ -696,6 +714,67 @@ class EPFFNPacked(torch.autograd.Function):
             gob = Fn._chunked_dense_colsum(dout, ctx.ob_dtype)
         return (dx2, dw, None, gk, gv, gb, gob, None, None, None, None, None, None,
                 dout if (ctx.has[2] and ctx.needs_input_grad[13]) else None, None)
+
+
+class EPFFNPackedSlots(torch.autograd.Function):
+    """EPFFNPacked that also returns the expert outputs per (token, k) slot, [T, K, Dout] -- functional.MoEFFNPackedSlots under expert
+    parallelism: the `topk` outputs of the pretrain competition step's diversity loss (moe_pretrain_model/layers/moe/competesmoe.py:
+    403-410), taken from the rows the owners sent back.  Same arguments as EPFFNPacked."""
+
+    @staticmethod
+    def forward(ctx, x2, w, idx, keys, values, bias, o_bias, act: int, combine_mode: int, E_global: int, group, chunks: int,
+                direct: bool, residual=None, stats=None):
+        from .functional import _SlotMap
+        out = EPFFNPacked.forward(ctx, x2, w, idx, keys, values, bias, o_bias, act, combine_mode, E_global, group, chunks, direct,
+                                  residual, stats)
+        bins, y = ctx.saved[0], ctx.saved[3]
+        y_tk = ops.dispatch_rows(y, _SlotMap(bins.slot_of, bins.n))        # y_tk[t*K+k] = y[slot_of[t*K+k]]
+        return out, y_tk.view(x2.shape[0], idx.shape[-1], y.shape[-1])
+
+    @staticmethod
+    def backward(ctx, dout, dy_tk):
+        from .functional import _SlotMap
+        if ctx.saved is None:
+            return EPFFNPacked._backward(ctx, dout)       # raises the second-backward error
+        bins = ctx.saved[0]
+        extra = None
+        if dy_tk is not None:                             # binned order, in the operand dtype: one more message per lane
+            extra = ops.dispatch_rows(dy_tk.reshape(bins.n, -1).to(ctx.op).contiguous(), _SlotMap(bins.perm, bins.n))
+        if dout is None:
+            dout = torch.zeros(ctx.w.shape[0], ctx.tab.Dout, dtype=ctx.op, device=ctx.w.device)
+        return EPFFNPacked._backward(ctx, dout, extra)
+
+
+# default of the local competition pass's dX chain, read once per process: 1 = every expert after the first adds its dX product into the
+# running sum in the GEMM epilogue (EPI_ACCUM); 0 = GEMM + torch add_ (the single-GPU chain; same bits)
+_COMP_DX_ACCUM = os.environ.get("CSMOE_COMP_DX_ACCUM", "1") != "0"
+
+
+class LocalCompetitionAffinity(torch.autograd.Function):
+    """The competition pass of THIS rank's packed experts over the gathered rows of all ranks: xa [P*T, D] -> [P*T, El].  Forward and
+    recompute backward are functional.CompetitionAffinityPacked's; the dX products of the local experts are chained into one buffer
+    with EPI_ACCUM (the first expert writes, the rest add, ascending expert order -- at world 1 the single-GPU chain bit for bit)."""
+
+    @staticmethod
+    def forward(ctx, xa, keys, values, act: int, fp32_affinity: bool):
+        from .functional import CompetitionAffinityPacked
+        return CompetitionAffinityPacked.forward(ctx, xa, keys, values, act, fp32_affinity)
+
+    @staticmethod
+    def backward(ctx, daff):
+        from .functional import CompetitionAffinityPacked
+        return CompetitionAffinityPacked._backward(ctx, daff, _COMP_DX_ACCUM)
+
+
+def local_competition_affinity(xa: torch.Tensor, keys: torch.Tensor, values: torch.Tensor, act: int, fp32_affinity: bool) -> torch.Tensor:
+    """Affinities [P*T, El] of the gathered rows to this rank's experts.  Where the affinity epilogues cannot run (ops.affinity_ok:
+    fp32 operands, odd sizes) each local expert is a DenseFFN over the gathered rows followed by SoftplusMean -- the stored form of
+    the single-GPU pass; only the affinities are kept, the selected outputs come from the sparse step either way."""
+    from .functional import DenseFFN, SoftplusMean
+    if ops.affinity_ok(xa, keys.shape[2], values.shape[2]):
+        return LocalCompetitionAffinity.apply(xa, keys, values, act, fp32_affinity)
+    return torch.stack([SoftplusMean.apply(DenseFFN.apply(xa, keys[e], None, values[e], None, act, L.B_KN), fp32_affinity)
+                        for e in range(keys.shape[0])], dim=-1)
 
 
 def reduce_grad_on_backward(param: torch.Tensor, group=None):

@@ -1037,6 +1037,12 @@ class CompetitionAffinityPacked(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, daff):
+        return CompetitionAffinityPacked._backward(ctx, daff, False)
+
+    @staticmethod
+    def _backward(ctx, daff, accum_dx: bool):
+        """`accum_dx`: every expert after the first ADDS its dX product into the running sum in the GEMM's epilogue (EPI_ACCUM) --
+        the same bits as the GEMM + `add_` chain, one pass over dx fewer per expert (ep.LocalCompetitionAffinity)."""
         x2, keys, values = ctx.saved_tensors
         act, fp32_affinity = ctx.cfg
         op = x2.dtype
@@ -1056,8 +1062,11 @@ class CompetitionAffinityPacked(torch.autograd.Function):
             if gk is not None:
                 gk[e] = _dense_wgrad(x2, dh, keys.dtype)
             if ctx.needs_input_grad[0]:
-                dxe = ops.dense_gemm(dh, k_e, _flip(L.B_KN))
-                dx = dxe if dx is None else dx.add_(dxe)
+                if accum_dx and dx is not None:
+                    ops.dense_gemm(dh, k_e, _flip(L.B_KN), epilogue=L.EPI_ACCUM, out=dx)
+                else:
+                    dxe = ops.dense_gemm(dh, k_e, _flip(L.B_KN))
+                    dx = dxe if dx is None else dx.add_(dxe)
             del hpre, hact, dy, dh
         return dx, gk, gv, None, None
 

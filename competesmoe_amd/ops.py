@@ -570,13 +570,22 @@ def f32w_ok(M: int, N: int, Kd: int) -> bool:
 
 def dense_gemm(A: torch.Tensor, B: torch.Tensor, b_layout: int, bias: Optional[torch.Tensor] = None,
                epilogue: int = L.EPI_PLAIN, act: int = L.ACT_NONE, aux: Optional[torch.Tensor] = None, want_c2: bool = False,
-               force_generic: bool = False, want_c: bool = True, kernel: int = 0):
+               force_generic: bool = False, want_c: bool = True, kernel: int = 0, out: Optional[torch.Tensor] = None):
+    """`out`: write C into this [M, N] tensor (rows may be strided) instead of a new one -- the operand of EPI_ACCUM, which adds
+    round(A @ B) to what `out` holds (torch's `out.add_(A @ B)`, bit for bit)."""
     M, Kd = A.shape
     N = B.shape[0] if b_layout == L.B_NK else B.shape[1]
-    Cm = torch.empty(M, N, dtype=A.dtype, device=A.device) if want_c else None
+    if epilogue == L.EPI_ACCUM and out is None:
+        raise ValueError("dense_gemm: EPI_ACCUM adds into `out`")
+    if out is not None:
+        if out.shape != (M, N) or out.dtype != A.dtype or out.stride(1) != 1 or not want_c or want_c2:
+            raise ValueError("dense_gemm: `out` must be an [M, N] tensor of A's dtype with unit column stride (C only)")
+        Cm, ldc = out, out.stride(0)
+    else:
+        Cm, ldc = (torch.empty(M, N, dtype=A.dtype, device=A.device) if want_c else None), N
     C2 = torch.empty(M, N, dtype=A.dtype, device=A.device) if want_c2 else None
     L.check(lib.csmoe_dense_gemm(A.data_ptr(), A.stride(0), B.data_ptr(), b_layout, B.stride(0), _ptr(bias), M, N, Kd,
-                                 _ptr(Cm), _ptr(C2), _ptr(aux), N, epilogue, act, _dt(A), 1 if force_generic else int(kernel), _stream()),
+                                 _ptr(Cm), _ptr(C2), _ptr(aux), ldc, epilogue, act, _dt(A), 1 if force_generic else int(kernel), _stream()),
             "dense_gemm")
     return (Cm, C2) if want_c2 else Cm
 

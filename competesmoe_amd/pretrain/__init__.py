@@ -9,6 +9,8 @@ from .deepseek import DeepSeekV2, DeepSeekV3
 from .smoe_perturbed import MoEPerturbedCosingGating, Selection
 from .block import MoEBlock
 from .smoe_ep import EPSMoeLayer
+from .competesmoe_ep import EPCompeteSMoE
 
 __all__ = ["register_moe", "get_moe", "MOE_REGISTRY", "LoggingLayer", "RegularizedLayer", "OncePerIterLayer", "CVMMSel", "cvmm",
-           "cvmm_prepare_sel2", "MoE", "SMoeLayer", "CompeteSMoE", "DeepSeekV2", "DeepSeekV3", "MoEPerturbedCosingGating", "Selection", "MoEBlock", "EPSMoeLayer"]
+           "cvmm_prepare_sel2", "MoE", "SMoeLayer", "CompeteSMoE", "DeepSeekV2", "DeepSeekV3", "MoEPerturbedCosingGating", "Selection", "MoEBlock", "EPSMoeLayer",
+           "EPCompeteSMoE"]

@@ -36,20 +36,24 @@ class CompeteSMoE(MoE):
         self.flip_steps = flip_steps
         if flip_steps <= 0:
             raise ValueError("self.total_steps - self.step_warm must be greater than 0.")
-        rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
-        device = self.w_gate.device
         cap = self.max_compete_in_iter
-        if rank == 0:
-            cur = draw_balanced_flips(flip_steps, self.rate_flip, cap, self.prob_flips_final)
-            probs_current = torch.tensor(cur, dtype=torch.bool, device=device)
-        else:
-            probs_current = torch.empty(flip_steps, dtype=torch.bool, device=device)
-        if world > 1:
-            dist.broadcast(probs_current, src=0)
+        probs_current = self._share_schedule(lambda: draw_balanced_flips(flip_steps, self.rate_flip, cap, self.prob_flips_final),
+                                             flip_steps, self.w_gate.device)
         self.prob_flips_final[id_layer] = probs_current
         self._flips_host = {}
         self.is_prob_flips = False
         return self.prob_flips_final
+
+    def _share_schedule(self, draw, n: int, device) -> torch.Tensor:
+        """The schedule [n] (bool), the same on every rank: drawn on global rank 0, broadcast over the default group."""
+        rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
+        if rank == 0:
+            probs_current = torch.tensor(draw(), dtype=torch.bool, device=device)
+        else:
+            probs_current = torch.empty(n, dtype=torch.bool, device=device)
+        if world > 1:
+            dist.broadcast(probs_current, src=0)
+        return probs_current
 
     def set_current_steps(self, step):
         self.current_steps = step

@@ -88,7 +88,14 @@ enum {
    * partial sums over column groups of round(acc)[m,n] * aux[m,n]; their row sums (csmoe_affinity_finish with D = 1) are the gradient
    * of the reduction weights as the reference forms it, `grad_x_full @ x` (cvmm.py:544) -- meaningful when aux is the activated
    * input of the second product (ReLU experts). */
-  CSMOE_EPI_ACTGRAD_ROWSCALE = 7
+  CSMOE_EPI_ACTGRAD_ROWSCALE = 7,
+  /* C[m,n] = round(C[m,n] + round(acc)) in bf16 (C += acc in fp32): the product is ADDED to what C holds -- bit for bit
+   * `C.add_(A @ B)` of two bf16 tensors, the running sum of the competition backward's per-expert dX chain
+   * (moe_pretrain_model/layers/moe/competesmoe.py:395-401 under autograd).  C is read in the epilogue (16-byte loads issued
+   * before the tile is staged through LDS), each tile is owned by one workgroup: no atomics, deterministic.  csmoe_dense_gemm only,
+   * on every kernel it can select (bias, C2 and aux must be null; ldc >= N); csmoe_grouped_gemm, csmoe_grouped_gemm_f32w and the
+   * MXFP8 entry points return CSMOE_ERR_UNSUPPORTED for it before launching anything, so C is never half-written. */
+  CSMOE_EPI_ACCUM = 8
 };
 
 int csmoe_version(void);
