@@ -182,8 +182,8 @@ int csmoe_gate_logits(const void* x, const void* w_gate, void* logits, int T, in
   if (T == 0) return CSMOE_OK;      // empty batch: zero-row buffers have no address
   hipStream_t st = (hipStream_t)stream;
   if (k_gate_small_ok(D, E, dtype, x, w_gate)) return k_gate_small_fwd(x, w_gate, logits, T, D, E, dtype, st);
-  // one dense "expert" over all T rows: logits = x @ w_gate^T
-  if (dtype == CSMOE_BF16 && gg_fast_rowspace_ok(D, D, E, T, E, D, x, logits))
+  // one dense "expert" over all T rows: logits = x @ w_gate^T (the tiled kernel reads w_gate in 16-byte pieces too)
+  if (dtype == CSMOE_BF16 && gg_fast_rowspace_ok(D, D, E, T, E, D, x, logits) && ((uintptr_t)w_gate & 15) == 0)
     return gg_fast_rowspace(x, D, nullptr, CSMOE_B_NK, D, nullptr, nullptr, 1, T, E, D, logits, nullptr, nullptr, E,
                             CSMOE_EPI_PLAIN, CSMOE_ACT_NONE, w_gate, nullptr, st);
   return gg_generic_rowspace(x, D, nullptr, CSMOE_B_NK, D, nullptr, nullptr, 1, T, E, D, logits, nullptr, nullptr, E,
@@ -258,21 +258,22 @@ int csmoe_gate_select(const void* x, const void* w_gate, int T, int D, int E, in
                        (hipStream_t)stream);
 }
 
+// 16-B vector path needs 16-B aligned rows; otherwise the kernel copies 2 bytes at a time
+int csmoe_dispatch_vec_ok(const void* x, const void* xs, int D, int dtype) {
+  const int row_bytes = D * esize(dtype);
+  return ((((uintptr_t)x | (uintptr_t)xs) & 15) == 0 && (row_bytes & 15) == 0) ? 1 : 0;
+}
+
 int csmoe_dispatch_rows(const void* x, const int32_t* perm, int K, void* xs, int n, int D, int dtype, csmoe_stream_t stream) {
   CSMOE_CHECK_ARG(dtype_ok(dtype) && K > 0 && n >= 0 && D > 0, "dispatch_rows: bad arguments");
   CSMOE_CHECK_ARG(n == 0 || (x && perm && xs), "dispatch_rows: null pointer");
-  int row_bytes = D * esize(dtype);
-  // 16-B vector path needs 16-B aligned rows; otherwise the kernel copies 2 bytes at a time
-  int vec_ok = ((((uintptr_t)x | (uintptr_t)xs) & 15) == 0 && (row_bytes & 15) == 0) ? 1 : 0;
-  return k_dispatch_rows(x, perm, K, xs, n, row_bytes, vec_ok, (hipStream_t)stream);
+  return k_dispatch_rows(x, perm, K, xs, n, D * esize(dtype), csmoe_dispatch_vec_ok(x, xs, D, dtype), (hipStream_t)stream);
 }
 
 int csmoe_dispatch_tokens(const void* x, const int32_t* slot_of, int K, void* xs, int T, int D, int dtype, csmoe_stream_t stream) {
   CSMOE_CHECK_ARG(dtype_ok(dtype) && K > 0 && T >= 0 && D > 0, "dispatch_tokens: bad arguments");
   CSMOE_CHECK_ARG(T == 0 || (x && slot_of && xs), "dispatch_tokens: null pointer");
-  int row_bytes = D * esize(dtype);
-  int vec_ok = ((((uintptr_t)x | (uintptr_t)xs) & 15) == 0 && (row_bytes & 15) == 0) ? 1 : 0;
-  return k_dispatch_tokens(x, slot_of, K, xs, T, row_bytes, vec_ok, (hipStream_t)stream);
+  return k_dispatch_tokens(x, slot_of, K, xs, T, D * esize(dtype), csmoe_dispatch_vec_ok(x, xs, D, dtype), (hipStream_t)stream);
 }
 
 int csmoe_dispatch_rows_bwd(const void* dxs, const int32_t* slot_of, int K, const void* add, void* dx, int T, int D, int dtype,
@@ -359,7 +360,7 @@ int csmoe_dense_gemm(const void* A, int64_t lda, const void* B, int b_layout, in
     CSMOE_CHECK_ARG(epilogue == CSMOE_EPI_SOFTPLUS_ROWSUM || aux, "dense_gemm: SOFTPLUS_GRAD needs aux (the FP32 row scales)");
     CSMOE_CHECK_ARG(!rowsum || ldc >= (N + 255) / 256, "dense_gemm: SOFTPLUS_ROWSUM: ldc is the row stride of the FP32 table [M, ceil(N/256)]");
     if (dtype != CSMOE_BF16 || !gg_fast_rowspace_ok(lda, ldb, rowsum ? (int64_t)N : ldc, M, N, Kd, A, rowsum ? A : C) ||
-        ((uintptr_t)C & 15)) {
+        (((uintptr_t)C | (uintptr_t)B) & 15)) {
       csmoe_set_error("dense_gemm: the affinity epilogues need bf16 operands on the fast path (dimensions multiples of 8, "
                       "16-byte aligned, under 2 GiB)");
       return CSMOE_ERR_UNSUPPORTED;
@@ -367,7 +368,9 @@ int csmoe_dense_gemm(const void* A, int64_t lda, const void* B, int b_layout, in
     return (use_v4_rowspace(Kd, b_layout, kernel) ? gg4_rowspace : gg8_rowspace)(A, lda, nullptr, b_layout, ldb, nullptr, nullptr, 1, M, N, Kd, C, C2,
                                                                        aux, ldc, epilogue, act, B, bias, st);
   }
-  if (kernel != CSMOE_KERNEL_GENERIC && dtype == CSMOE_BF16 && gg_fast_rowspace_ok(lda, ldb, ldc, M, N, Kd, A, C ? C : C2))
+  // the single B is a host-visible pointer here (the grouped entry's per-expert table is not): its alignment picks the kernel too
+  if (kernel != CSMOE_KERNEL_GENERIC && dtype == CSMOE_BF16 && gg_fast_rowspace_ok(lda, ldb, ldc, M, N, Kd, A, C ? C : C2) &&
+      ((uintptr_t)B & 15) == 0)
     return pick_rowspace(M, N, Kd, b_layout, kernel)(A, lda, nullptr, b_layout, ldb, nullptr, nullptr, 1, M, N, Kd, C, C2, aux, ldc, epilogue, act, B,
                                            bias, st);
   return gg_generic_rowspace(A, lda, nullptr, b_layout, ldb, nullptr, nullptr, 1, M, N, Kd, C, C2, aux, ldc, epilogue, act,
@@ -442,7 +445,7 @@ int csmoe_dense_wgrad(const void* A, int64_t lda, const void* B, int64_t ldb, in
   CSMOE_CHECK_ARG(C && (M == 0 || (A && B)), "dense_wgrad: null pointer");
   CSMOE_CHECK_ARG(!(dtype == CSMOE_F32 && out_dtype != CSMOE_F32), "dense_wgrad: fp32 inputs need fp32 output");
   hipStream_t st = (hipStream_t)stream;
-  if (!force_generic && dtype == CSMOE_BF16 && gg_fast_wgrad_ok(lda, ldb, ldc, M, Na, Nb, A, B)) {
+  if (!force_generic && dtype == CSMOE_BF16 && gg_fast_wgrad_ok(lda, ldb, ldc, M, Na, Nb, A, B) && ((uintptr_t)C & 15) == 0) {
     if (use_v2_wgrad(M, Na, Nb))
       return gg8_wgrad(A, lda, B, ldb, nullptr, 1, Na, Nb, nullptr, ldc, out_dtype, accumulate, M, C, st);
     return gg_fast_wgrad(A, lda, B, ldb, nullptr, 1, Na, Nb, nullptr, ldc, out_dtype, accumulate, M, C, st);
@@ -724,8 +727,10 @@ int csmoe_grouped_gemm_f32w(const void* A, int64_t lda, const void* const* b_ptr
   // With a bf16 copy requested: the launch over every expert's FIRST row tile converts the fp32 masters in its tile fill and writes
   // the copy; the other row tiles run the LDS-DMA kernel over that copy (same stream: the copy is complete when they start).
   // CSMOE_F32W_SPLIT=0 (A/B): every row tile converts, as in round 2.
+  // The bf16 copy of one expert (Kd x N, row stride N) is always under 2 GiB once the check above has passed: ldb >= N makes
+  // Kd * N * 2 <= Kd * ldb * 2 < 2^30, so the copy needs no size condition of its own.
   static const bool split = [] { const char* e = getenv("CSMOE_F32W_SPLIT"); return !e || atoi(e) != 0; }();
-  if (b_copy_ptrs && split && (int64_t)Kd * N * 2 < 0x80000000ll) {
+  if (b_copy_ptrs && split) {
     if (int rc = gg8c_rowspace(A, lda, b_ptrs, ldb, b_copy_ptrs, bias_ptrs, offsets, E, M, N, Kd, C, C2, aux, ldc, epilogue, act, nullptr,
                                nullptr, nullptr, (hipStream_t)stream, 1))
       return rc;

@@ -671,16 +671,24 @@ class EPFFNPacked(torch.autograd.Function):
             aux = hpre if hpre is not None else hact
             if scale_after:
                 wr = ln.arrived(w_s[0]).view(-1)
-                dot = None
+                dot = col = None
                 if use_dot and dys.shape[0]:
                     dc = ops.rowdot_cols(dys.shape[0], F, Dout, Dout, Dout, F, op)
-                    if dc == 0:
-                        raise RuntimeError("competesmoe_amd: EPFFNPacked: this rank's dH launch writes no dot table while the group's does")
-                    dot = torch.empty(dys.shape[0], dc, dtype=torch.float32, device=dev)
+                    if dc:
+                        dot = torch.empty(dys.shape[0], dc, dtype=torch.float32, device=dev)
+                    else:
+                        # this lane's dH launch writes no dot table (its rows push A past the fast kernel's 2 GiB limit) while the
+                        # group's launches do: the column in three steps, as _CVMM.backward's fallback forms it; same exchange shape
+                        prod = ops.grouped_gemm(dys, tab.w2_ptrs[e0:e1], L.B_NK, Dout, F, lb.offsets, Ec)
+                        col = (prod.float() * hact.float()).sum(-1).view(-1, 1)
+                        del prod
                 dh = ops.grouped_gemm(dys, tab.w2_ptrs[e0:e1], L.B_NK, Dout, F, lb.offsets, Ec, epilogue=L.EPI_ACTGRAD_ROWSCALE, act=tab.act,
                                       aux=aux, row_scale=wr, row_dot=dot)
                 if use_dot:
-                    col = ops.finish_row_dot(dot).view(-1, 1) if dot is not None else torch.empty(0, 1, dtype=torch.float32, device=dev)
+                    if dot is not None:
+                        col = ops.finish_row_dot(dot).view(-1, 1)
+                    elif col is None:
+                        col = torch.empty(0, 1, dtype=torch.float32, device=dev)
                     back.append(ln.give_back(col, dots))
                 if ex is not None:                       # the unweighted per-slot rows: their own product, added to dH
                     dh = dh + ops.grouped_gemm(ex.contiguous(), tab.w2_ptrs[e0:e1], L.B_NK, Dout, F, lb.offsets, Ec, epilogue=L.EPI_ACTGRAD,

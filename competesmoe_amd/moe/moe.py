@@ -74,8 +74,16 @@ class Route(NamedTuple):
 
 class MoeLayer(nn.Module):
 
+    @staticmethod
+    def _dense_input(module, args):
+        """The kernels read x as dense rows: a view (a column slice of a wider buffer) is made dense once, before forward()."""
+        if args and isinstance(args[0], torch.Tensor) and not args[0].is_contiguous():
+            return (args[0].contiguous(),) + tuple(args[1:])
+        return None
+
     def __init__(self, in_embed_dim=768, out_embed_dim=768, num_of_experts=4, num_selected=2, expert=None, args=None):
         super().__init__()
+        self.register_forward_pre_hook(MoeLayer._dense_input)
         self.in_embed_dim = in_embed_dim
         self.out_embed_dim = out_embed_dim
         self.num_of_experts = num_of_experts

@@ -64,6 +64,17 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _rows(what: str, *ts):
+    """The C ABI reads every tensor operand as dense row-major memory from its data_ptr(): a column slice, a transposed or an
+    expanded view would be read as the wrong elements, silently.  Refused here, before anything is launched; the layers make their
+    input dense once (x.contiguous() at the layer boundary).  Base alignment is the C ABI's business (it picks a scalar kernel or
+    refuses)."""
+    for t in ts:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"csmoe {what}: operands must be dense row-major tensors (got shape {tuple(t.shape)}, strides "
+                             f"{t.stride()}); pass .contiguous()")
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -91,6 +102,7 @@ def ptr_array(tensors: Sequence[Optional[torch.Tensor]], device) -> torch.Tensor
 # ------------------------------------------------------------------------------------------------ router
 def gate_logits(x2: torch.Tensor, w_gate: torch.Tensor) -> torch.Tensor:
     _need_cuda(x2, w_gate)
+    _rows("gate_logits", x2, w_gate)
     T, D = x2.shape
     E = w_gate.shape[0]
     out = torch.empty(T, E, dtype=x2.dtype, device=x2.device)
@@ -121,7 +133,8 @@ def gate_select_ok(x2: torch.Tensor, w_gate: torch.Tensor, K: int) -> bool:
     if os.environ.get("CSMOE_FUSED_ROUTER", "1") == "0" or not x2.is_cuda:
         return False
     T, D = x2.shape
-    return bool(lib.csmoe_gate_select_ok(T, D, w_gate.shape[0], K, _dt(x2))) and x2.data_ptr() % 16 == 0 and w_gate.data_ptr() % 16 == 0
+    return (bool(lib.csmoe_gate_select_ok(T, D, w_gate.shape[0], K, _dt(x2))) and x2.data_ptr() % 16 == 0 and w_gate.data_ptr() % 16 == 0
+            and x2.is_contiguous() and w_gate.is_contiguous())
 
 
 def gate_select(x2: torch.Tensor, w_gate: torch.Tensor, K: int, mode: int, round_sum_bf16: bool, want_softmax: bool = True,
@@ -130,6 +143,7 @@ def gate_select(x2: torch.Tensor, w_gate: torch.Tensor, K: int, mode: int, round
     the ids per block of rows; the bin_tokens call that sorts this `idx` (unmodified) picks the histogram up and skips its counting
     pass."""
     _need_cuda(x2, w_gate)
+    _rows("gate_select", x2, w_gate)
     T, D = x2.shape
     E = w_gate.shape[0]
     dev = x2.device
@@ -149,6 +163,7 @@ def gate_select(x2: torch.Tensor, w_gate: torch.Tensor, K: int, mode: int, round
 
 def router_select(scores: torch.Tensor, K: int, mode: int, round_sum_bf16: bool, want_softmax: bool = True, param: float = 1.0):
     _need_cuda(scores)
+    _rows("router_select", scores)
     T, E = scores.shape
     sm = torch.empty(T, E, dtype=torch.float32, device=scores.device) if want_softmax else None
     idx = torch.empty(T, K, dtype=torch.int32, device=scores.device)
@@ -159,6 +174,7 @@ def router_select(scores: torch.Tensor, K: int, mode: int, round_sum_bf16: bool,
 
 
 def router_select_bwd(scores, K, mode, round_sum_bf16, sm, idx, w, dw, dsm, param: float = 1.0):
+    _rows("router_select_bwd", scores, sm, idx, w, dw, dsm)
     T, E = scores.shape
     out = torch.empty_like(scores)
     L.check(lib.csmoe_router_select_bwd(scores.data_ptr(), _dt(scores), T, E, K, mode, int(round_sum_bf16), float(param), _ptr(sm),
@@ -171,6 +187,7 @@ def router_aux(logits: Optional[torch.Tensor], sm: torch.Tensor, idx: torch.Tens
     """(out2 [2] fp32 = balance, z; dens [B,E] fp32; lse [B*N] fp32 | None) of csmoe_router_aux for sm [B,N,E] fp32, idx [B,N,K]
     int32 and (optionally) the logits [B,N,E] whose softmax sm is."""
     _need_cuda(sm, idx, logits)
+    _rows("router_aux", logits, sm, idx)
     B, N, E = sm.shape
     K = idx.shape[-1]
     dev = sm.device
@@ -188,6 +205,7 @@ def router_aux(logits: Optional[torch.Tensor], sm: torch.Tensor, idx: torch.Tens
 def router_aux_bwd(sm: torch.Tensor, dens: torch.Tensor, lse: Optional[torch.Tensor], g_bal: Optional[torch.Tensor],
                    g_z: Optional[torch.Tensor], logits_dtype):
     """(dsoftmax fp32 | None, dlogits logits_dtype | None) of csmoe_router_aux_bwd; g_bal / g_z are 1-element fp32 device tensors."""
+    _rows("router_aux_bwd", sm, dens, lse)
     B, N, E = sm.shape
     dsm = torch.empty_like(sm) if g_bal is not None else None
     dlogits = torch.empty(B, N, E, dtype=logits_dtype, device=sm.device) if (g_z is not None and lse is not None) else None
@@ -321,6 +339,7 @@ def bin_tokens(idx: torch.Tensor, E: int, hist=None) -> Bins:
 
 # ------------------------------------------------------------------------------------------------ dispatch / combine
 def dispatch_rows(x2: torch.Tensor, bins: Bins) -> torch.Tensor:
+    _rows("dispatch_rows", x2)
     T, D = x2.shape
     xs = torch.empty(bins.n, D, dtype=x2.dtype, device=x2.device)
     with _timed("dispatch_rows", (T + bins.n) * D * x2.element_size()):     # read D, write K*D per token
@@ -331,6 +350,7 @@ def dispatch_rows(x2: torch.Tensor, bins: Bins) -> torch.Tensor:
 
 def dispatch_tokens(x2: torch.Tensor, bins: Bins) -> torch.Tensor:
     """Token-major dispatch: same xs as dispatch_rows, x fetched from HBM once per token."""
+    _rows("dispatch_tokens", x2)
     T, D = x2.shape
     xs = torch.empty(bins.n, D, dtype=x2.dtype, device=x2.device)
     with _timed("dispatch_rows", (T + bins.n) * D * x2.element_size()):
@@ -344,6 +364,7 @@ def dispatch_rows_bwd(dxs: torch.Tensor, bins: Bins, T: int, add: Optional[torch
     """dx[t] = round(round(sum_k dxs[slot]) + add[t]); with `idx` [T, K] (int32) the sequential form of the LLaVA stack's autograd:
     (((pre[t] + dxs[slot of the highest expert]) + ...) + dxs[slot of the lowest]) + add[t], rounded after every add (csmoe.h).
     `out_f32` (bf16 rows, D % 8 == 0): dx fp32 = float(round_bf16(sum_k dxs[slot])) + float(add[t]) (csmoe_dispatch_rows_bwd_mixed)."""
+    _rows("dispatch_rows_bwd", dxs, add, idx, pre)
     D = dxs.shape[1]
     if out_f32:
         if dxs.dtype != torch.bfloat16 or idx is not None or pre is not None:
@@ -394,6 +415,7 @@ def widen_sum(streams) -> torch.Tensor:
 
 def combine(y: torch.Tensor, bins: Bins, idx: torch.Tensor, w: torch.Tensor, mode: int, T: int,
             obias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _rows("combine", y, idx, w, obias, residual)
     D = y.shape[1]
     if residual is not None and residual.dtype == torch.float32 and y.dtype == torch.bfloat16:
         # fp32 residual stream around bf16 activations (pretrain stack under autocast): fp32 output, no cast passes
@@ -416,6 +438,7 @@ def combine(y: torch.Tensor, bins: Bins, idx: torch.Tensor, w: torch.Tensor, mod
 def layernorm_gate(x2: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float,
                    w_gate: Optional[torch.Tensor] = None):
     """xn, mean, rstd[, logits] = LayerNorm(x2) [and xn @ w_gate^T] -- csmoe_layernorm_gate."""
+    _rows("layernorm_gate", x2, gamma, beta, w_gate)
     T, D = x2.shape
     xn = torch.empty_like(x2)
     mean = torch.empty(T, dtype=torch.float32, device=x2.device)
@@ -435,6 +458,7 @@ def layernorm_gate(x2: torch.Tensor, gamma: Optional[torch.Tensor], beta: Option
 def layernorm_gate_mixed(x2: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float,
                          w_gate: Optional[torch.Tensor] = None):
     """fp32 x / gamma / beta -> bf16 xn (+ bf16 logits), fp32 mean / rstd -- csmoe_layernorm_gate_mixed."""
+    _rows("layernorm_gate_mixed", x2, gamma, beta, w_gate)
     T, D = x2.shape
     assert x2.dtype == torch.float32 and (gamma is None or gamma.dtype == torch.float32) and (beta is None or beta.dtype == torch.float32)
     xn = torch.empty(T, D, dtype=torch.bfloat16, device=x2.device)
@@ -454,6 +478,7 @@ def layernorm_gate_mixed(x2: torch.Tensor, gamma: Optional[torch.Tensor], beta: 
 def layernorm_bwd_mixed(dxn: torch.Tensor, x2: torch.Tensor, gamma: Optional[torch.Tensor], mean: torch.Tensor, rstd: torch.Tensor,
                         add: Optional[torch.Tensor] = None, want_affine_grads: bool = True, dxn2: Optional[torch.Tensor] = None):
     """fp32 dx [T,D] (+ fp32 add), dgamma / dbeta [D] fp32 from bf16 gradient stream(s) of xn and fp32 x."""
+    _rows("layernorm_bwd_mixed", dxn, x2, gamma, mean, rstd, add, dxn2)
     T, D = x2.shape
     assert dxn.dtype == torch.bfloat16 and x2.dtype == torch.float32 and (add is None or add.dtype == torch.float32)
     assert dxn2 is None or dxn2.dtype == torch.bfloat16
@@ -473,6 +498,7 @@ def layernorm_bwd_mixed(dxn: torch.Tensor, x2: torch.Tensor, gamma: Optional[tor
 def layernorm_bwd(dxn: torch.Tensor, x2: torch.Tensor, gamma: Optional[torch.Tensor], mean: torch.Tensor, rstd: torch.Tensor,
                   add: Optional[torch.Tensor] = None, want_affine_grads: bool = True, dxn2: Optional[torch.Tensor] = None):
     """dx [T,D] (+ add), dgamma [D] fp32, dbeta [D] fp32 -- csmoe_layernorm_bwd + the column sums of its partial rows."""
+    _rows("layernorm_bwd", dxn, x2, gamma, mean, rstd, add, dxn2)
     T, D = x2.shape
     dx = torch.empty_like(x2)
     nb = int(lib.csmoe_layernorm_bwd_blocks(T))
@@ -492,6 +518,7 @@ def combine_bwd(dout: torch.Tensor, y: Optional[torch.Tensor], bins: Bins, w: to
     """`act_dtype` = dtype of the expert rows when it differs from dout's (fp32 upstream gradient, bf16 rows).
     `round_products`: d w as autograd forms it when the weights are an x.dtype tensor (competition steps): every product
     dout * y rounded to the dtype, the sum rounded once."""
+    _rows("combine_bwd", dout, y, w)
     T, D = dout.shape
     if act_dtype == torch.bfloat16 and dout.dtype == torch.float32:
         dy = torch.empty(bins.n, D, dtype=torch.bfloat16, device=dout.device)
@@ -687,6 +714,7 @@ SOFTPLUS_PRECISE = os.environ.get("CSMOE_SOFTPLUS_PRECISE", "0") == "1"
 
 def softplus_mean(y: torch.Tensor, aff_dtype=None) -> torch.Tensor:
     """aff_dtype: y.dtype (x.dtype tensor-op semantics) or torch.float32 around bf16 rows (CUDA-autocast semantics)."""
+    _rows("softplus_mean", y)
     R, D = y.shape
     aff = torch.empty(R, dtype=aff_dtype or y.dtype, device=y.device)
     L.check(lib.csmoe_softplus_mean(y.data_ptr(), aff.data_ptr(), R, D, _dt(y), _dt(aff), int(SOFTPLUS_PRECISE), _stream()), "softplus_mean")
@@ -694,6 +722,7 @@ def softplus_mean(y: torch.Tensor, aff_dtype=None) -> torch.Tensor:
 
 
 def softplus_mean_bwd(y: torch.Tensor, daff: torch.Tensor, dy_add: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _rows("softplus_mean_bwd", y, daff, dy_add)
     R, D = y.shape
     dy = torch.empty_like(y)
     L.check(lib.csmoe_softplus_mean_bwd(y.data_ptr(), daff.data_ptr(), _ptr(dy_add), dy.data_ptr(), R, D, _dt(y), _dt(daff),
@@ -703,6 +732,7 @@ def softplus_mean_bwd(y: torch.Tensor, daff: torch.Tensor, dy_add: Optional[torc
 
 def pair_cosine(y3: torch.Tensor) -> torch.Tensor:
     """tok_loss[T] (fp32) of csmoe_pair_cosine for y3 [T, K, D]."""
+    _rows("pair_cosine", y3)
     T, K, D = y3.shape
     out = torch.empty(T, dtype=torch.float32, device=y3.device)
     with _timed("pair_cosine", T * K * D * y3.element_size()):
@@ -711,6 +741,7 @@ def pair_cosine(y3: torch.Tensor) -> torch.Tensor:
 
 
 def pair_cosine_bwd(y3: torch.Tensor, gscale: torch.Tensor) -> torch.Tensor:
+    _rows("pair_cosine_bwd", y3, gscale)
     T, K, D = y3.shape
     dy = torch.empty_like(y3)
     with _timed("pair_cosine_bwd", 2 * T * K * D * y3.element_size()):

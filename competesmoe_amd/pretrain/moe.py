@@ -171,6 +171,10 @@ class MoE(LoggingLayer, RegularizedLayer, OncePerIterLayer, nn.Module):
     @staticmethod
     def _enter_forward(module, args):
         module._twins, module._forking = None, True
+        # the kernels read x as dense rows: a view (a column slice of a wider buffer) is made dense once, here, for every consumer
+        if args and isinstance(args[0], torch.Tensor) and not args[0].is_contiguous():
+            return (args[0].contiguous(),) + tuple(args[1:])
+        return None
 
     @staticmethod
     def _leave_forward(module, args, output):

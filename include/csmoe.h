@@ -167,6 +167,9 @@ int csmoe_dispatch_rows(const void* x, const int32_t* perm, int K, void* xs, int
 /* token-major dispatch (same result; reads every x row from HBM once): xs[slot_of[t*K+k], :] = x[t, :] */
 int csmoe_dispatch_tokens(const void* x, const int32_t* slot_of, int K, void* xs, int T, int D, int dtype,
                           csmoe_stream_t stream);
+/* Kernel choice of the two dispatch entries: 1 = the 16-byte vector copy (x and xs 16-byte aligned, rows a multiple of 16 bytes),
+ * 0 = the 2-byte copy.  Both copy the same bytes. */
+int csmoe_dispatch_vec_ok(const void* x, const void* xs, int D, int dtype);
 /* dispatch backward: dx[t,:] = round(round(sum_k dxs[slot_of[t*K+k], :]) + add[t,:])  (add may be null): the K-sum in fp32, rounded
  * once -- CVMM.backward's reduction (cvmm.py:544-545) and, for K <= 2, the LLaVA stack's autograd.
  * `idx` [T,K] != null selects what autograd does for the LLaVA stack's per-expert modules (moe.py:196-204): every expert's `x[...]`

@@ -87,6 +87,17 @@ def _worker(rank, world, port, backend, cfg, q):
         from competesmoe_amd.pretrain import MoEBlock, get_moe
         if backend == "gloo":
             _host_collectives()
+        from competesmoe_amd import ops
+        real_rowdot = ops.rowdot_cols
+        res["fallbacks"] = 0
+
+        def rowdot_refused(M, *a):
+            # a dH launch of any row count but the one the group decides from (256) writes no dot table: as when a rank receives
+            # enough rows to push the operand past the tiled kernel's 2 GiB limit
+            if M != 256:
+                res["fallbacks"] += 1
+                return 0
+            return real_rowdot(M, *a)
         dt_name = cfg["dt"]
         autocast = dt_name == "bf16"
         bias, block, empty = cfg.get("bias", False), cfg.get("block", False), cfg.get("empty", False)
@@ -149,7 +160,12 @@ def _worker(rank, world, port, backend, cfg, q):
                         return _orig(x_, idx_, w_)
                     setattr(lay, meth, spy)
             oa, ra = step(mod_a, full, xa)
-            ob, rb = step(mod_b, epl, xb)
+            if cfg.get("rowdot_refused") == rank:
+                ops.rowdot_cols = rowdot_refused
+            try:
+                ob, rb = step(mod_b, epl, xb)
+            finally:
+                ops.rowdot_cols = real_rowdot
             for lay in (full, epl):
                 lay.__dict__.pop("ffn_slots", None)
                 lay.__dict__.pop("compute_moe_main", None)
@@ -224,6 +240,7 @@ CASES = [
     (2, "gloo", dict(dt="bf16", chunks=2, empty=True)),
     (2, "gloo", dict(dt="bf16", block=True)),
     (2, "gloo", dict(dt="fp32", chunks=2, direct=True)),
+    (2, "gloo", dict(dt="bf16", rowdot_refused=1)),
     (4, "gloo", dict(dt="bf16", chunks=2, direct=True, variant="hybrid")),
 ]
 
@@ -239,6 +256,8 @@ def test_pretrain_competesmoe_ep_equals_single_gpu(world, backend, cfg):
     for r in range(world):
         m = res[r]
         assert "error" not in m, m
+        if cfg.get("rowdot_refused") == r:       # that rank's lanes took the local dot column (ep.py), its peer the dot table
+            assert m["fallbacks"] > 0, m
         for step in ("router", "comp"):
             assert m[f"{step}_idx"], (r, step, m)
             if lean_ref or step == "router":
