@@ -324,9 +324,19 @@ int csmoe_grouped_gemm(const void* A, int64_t lda, const void* const* b_ptrs, in
                   "grouped_gemm: bad kernel selector %d", kernel);
   // ACTGRAD_ROWSCALE with a dot table (passed in the bias slot): only the tiled bf16 kernels fill it
   const bool wants_dot = epilogue == CSMOE_EPI_ACTGRAD_ROWSCALE && bias_ptrs != nullptr;
-  if (kernel != CSMOE_KERNEL_GENERIC && dtype == CSMOE_BF16 && gg_fast_rowspace_ok(lda, ldb, ldc, M, N, Kd, A, C ? C : C2))
-    return pick_rowspace(M, N, Kd, b_layout, kernel)(A, lda, b_ptrs, b_layout, ldb, bias_ptrs, offsets, E, M, N, Kd, C, C2, aux, ldc, epilogue, act,
-                                           nullptr, nullptr, st);
+  if (kernel != CSMOE_KERNEL_GENERIC && dtype == CSMOE_BF16 && gg_fast_rowspace_ok(lda, ldb, ldc, M, N, Kd, A, C ? C : C2)) {
+    const rowspace_fn fn = pick_rowspace(M, N, Kd, b_layout, kernel);
+    // the caller sized (and will read) the dot table by csmoe_grouped_gemm_rowdot_cols, which knows the shape but not `kernel`: a
+    // 256-tile kernel writes [M][ceil(N/128)], the 128-tile kernel [M][N/8]
+    const int dot_cols = fn == gg_fast_rowspace ? N / 8 : (N + 127) / 128;
+    if (wants_dot && dot_cols != csmoe_grouped_gemm_rowdot_cols(M, N, Kd, lda, ldb, ldc, dtype)) {
+      csmoe_set_error("grouped_gemm: ACTGRAD_ROWSCALE was given a dot table, but kernel %d at M=%d N=%d Kd=%d writes %d partial sums "
+                      "per row where csmoe_grouped_gemm_rowdot_cols reports %d", kernel, M, N, Kd, dot_cols,
+                      csmoe_grouped_gemm_rowdot_cols(M, N, Kd, lda, ldb, ldc, dtype));
+      return CSMOE_ERR_UNSUPPORTED;
+    }
+    return fn(A, lda, b_ptrs, b_layout, ldb, bias_ptrs, offsets, E, M, N, Kd, C, C2, aux, ldc, epilogue, act, nullptr, nullptr, st);
+  }
   if (wants_dot) {
     csmoe_set_error("grouped_gemm: ACTGRAD_ROWSCALE was given a dot table, but this launch (dtype %d, alignment, kernel %d) runs on the "
                     "generic kernel, which writes none (csmoe_grouped_gemm_rowdot_cols reports 0 for it)", dtype, kernel);

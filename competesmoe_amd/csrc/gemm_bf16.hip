@@ -253,11 +253,13 @@ __global__ void __launch_bounds__(256, 2) gg_fast_kernel(FastArgs p) {
   }
 }
 
-template <typename K>
-int set_lds(K kern) {
+// one flag per kernel instantiation: keyed on the kernel itself, not on its function-pointer type (which every instantiation
+// shares, so a `static bool` inside a function template on that type was set by the first launch of any of them)
+template <auto Kern>
+int set_lds() {
   static bool done = false;
   if (!done) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    hipError_t e = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     if (e != hipSuccess) { csmoe_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return CSMOE_ERR_LAUNCH; }
     done = true;
   }
@@ -288,10 +290,10 @@ int gg_fast_rowspace(const void* A, int64_t lda, const void* const* b_ptrs, int 
   if (grid > 0x7fffffff) { csmoe_set_error("grouped_gemm: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
   int rc;
   if (b_layout == CSMOE_B_NK) {
-    if ((rc = set_lds(gg_fast_kernel<KC, KC, 0>))) return rc;
+    if ((rc = set_lds<gg_fast_kernel<KC, KC, 0>>())) return rc;
     hipLaunchKernelGGL((gg_fast_kernel<KC, KC, 0>), dim3((unsigned)grid), dim3(256), LDS_BYTES, st, p);
   } else {
-    if ((rc = set_lds(gg_fast_kernel<KC, KM, 0>))) return rc;
+    if ((rc = set_lds<gg_fast_kernel<KC, KM, 0>>())) return rc;
     hipLaunchKernelGGL((gg_fast_kernel<KC, KM, 0>), dim3((unsigned)grid), dim3(256), LDS_BYTES, st, p);
   }
   CSMOE_CHECK_LAUNCH("grouped_gemm(bf16)");
@@ -316,7 +318,7 @@ int gg_fast_wgrad(const void* A, int64_t lda, const void* B, int64_t ldb, const 
   if (grid <= 0) return CSMOE_OK;
   if (grid > 0x7fffffff) { csmoe_set_error("grouped_wgrad: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
   int rc;
-  if ((rc = set_lds(gg_fast_kernel<KM, KM, 1>))) return rc;
+  if ((rc = set_lds<gg_fast_kernel<KM, KM, 1>>())) return rc;
   hipLaunchKernelGGL((gg_fast_kernel<KM, KM, 1>), dim3((unsigned)grid), dim3(256), LDS_BYTES, st, p);
   CSMOE_CHECK_LAUNCH("grouped_wgrad(bf16)");
   return CSMOE_OK;

@@ -353,11 +353,12 @@ int sched_pref(int b_layout) {
   return b_layout == CSMOE_B_NK ? BAL : WIDE;
 }
 
-template <typename K>
-int set_lds2(K kern) {
+// one flag per kernel instantiation (keyed on the kernel, not on the function-pointer type all instantiations share)
+template <auto Kern>
+int set_lds2() {
   static bool done = false;
   if (!done) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2_BYTES);
+    hipError_t e = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2_BYTES);
     if (e != hipSuccess) { csmoe_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return CSMOE_ERR_LAUNCH; }
     done = true;
   }
@@ -407,19 +408,19 @@ static int rowspace_launch(const void* A, int64_t lda, const void* const* b_ptrs
 #define LAUNCH_SCHED(S)                                                                                              \
   do {                                                                                                                \
     if (b_layout == CSMOE_B_NK) {                                                                                     \
-      if ((rc = set_lds2(gg8_kernel<KC, KC, 0, S>))) return rc;                                                       \
+      if ((rc = set_lds2<gg8_kernel<KC, KC, 0, S>>())) return rc;                                                       \
       hipLaunchKernelGGL((gg8_kernel<KC, KC, 0, S>), dim3((unsigned)grid), dim3(512), LDS2_BYTES, st, p);             \
     } else {                                                                                                          \
-      if ((rc = set_lds2(gg8_kernel<KC, KM, 0, S>))) return rc;                                                       \
+      if ((rc = set_lds2<gg8_kernel<KC, KM, 0, S>>())) return rc;                                                       \
       hipLaunchKernelGGL((gg8_kernel<KC, KM, 0, S>), dim3((unsigned)grid), dim3(512), LDS2_BYTES, st, p);             \
     }                                                                                                                 \
   } while (0)
   if (epilogue == CSMOE_EPI_ACCUM) {      // each layout with its default schedule (sched_pref without CSMOE_GEMM_SCHED)
     if (b_layout == CSMOE_B_NK) {
-      if ((rc = set_lds2(gg8_kernel<KC, KC, 0, BAL, true>))) return rc;
+      if ((rc = set_lds2<gg8_kernel<KC, KC, 0, BAL, true>>())) return rc;
       hipLaunchKernelGGL((gg8_kernel<KC, KC, 0, BAL, true>), dim3((unsigned)grid), dim3(512), LDS2_BYTES, st, p);
     } else {
-      if ((rc = set_lds2(gg8_kernel<KC, KM, 0, WIDE, true>))) return rc;
+      if ((rc = set_lds2<gg8_kernel<KC, KM, 0, WIDE, true>>())) return rc;
       hipLaunchKernelGGL((gg8_kernel<KC, KM, 0, WIDE, true>), dim3((unsigned)grid), dim3(512), LDS2_BYTES, st, p);
     }
   } else if (sp == BAL) LAUNCH_SCHED(BAL); else LAUNCH_SCHED(WIDE);

@@ -297,11 +297,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 #endif
 }
 
-template <typename K>
-int set_lds4(K kern) {
+// one flag per kernel instantiation (keyed on the kernel, not on the function-pointer type all instantiations share)
+template <auto Kern>
+int set_lds4() {
   static bool done = false;
   if (!done) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4_BYTES);
+    hipError_t e = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4_BYTES);
     if (e != hipSuccess) { csmoe_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return CSMOE_ERR_LAUNCH; }
     done = true;
   }
@@ -328,13 +329,13 @@ int gg4_rowspace(const void* A, int64_t lda, const void* const* b_ptrs, int b_la
   if (grid > 0x7fffffff) { csmoe_set_error("grouped_gemm: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
   int rc;
   if (epilogue == CSMOE_EPI_ACCUM) {      // K-contiguous weights only (gg4_rowspace_ok)
-    if ((rc = set_lds4(gg4_kernel<KC, true>))) return rc;
+    if ((rc = set_lds4<gg4_kernel<KC, true>>())) return rc;
     hipLaunchKernelGGL((gg4_kernel<KC, true>), dim3((unsigned)grid), dim3(256), LDS4_BYTES, st, p);
   } else if (b_layout == CSMOE_B_NK) {
-    if ((rc = set_lds4(gg4_kernel<KC>))) return rc;
+    if ((rc = set_lds4<gg4_kernel<KC>>())) return rc;
     hipLaunchKernelGGL((gg4_kernel<KC>), dim3((unsigned)grid), dim3(256), LDS4_BYTES, st, p);
   } else {
-    if ((rc = set_lds4(gg4_kernel<KM>))) return rc;
+    if ((rc = set_lds4<gg4_kernel<KM>>())) return rc;
     hipLaunchKernelGGL((gg4_kernel<KM>), dim3((unsigned)grid), dim3(256), LDS4_BYTES, st, p);
   }
   CSMOE_CHECK_LAUNCH("grouped_gemm(bf16 v4)");

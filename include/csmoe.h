@@ -204,7 +204,10 @@ int csmoe_combine_bwd(const void* dout, const void* y, const int32_t* perm, cons
  * 256x256 kernel, the 128x128 kernel for small / narrow problems, the generic kernel for fp32 and unaligned operands); 1 forces the
  * generic kernel; 2 / 4 ask for the 8-wave / one-wave-per-SIMD kernel where the shape allows (tests and A/B runs: every kernel is
  * reachable through the interface, none through hidden state).  A CSMOE_EPI_ACTGRAD_ROWSCALE launch that passes a dot table and
- * lands on a kernel that cannot fill it returns CSMOE_ERR_UNSUPPORTED instead of leaving the table unwritten. */
+ * lands on a kernel that cannot fill it returns CSMOE_ERR_UNSUPPORTED instead of leaving the table unwritten; so does one whose
+ * kernel would write a different table layout from the one csmoe_grouped_gemm_rowdot_cols reports for the shape (that function does
+ * not take `kernel`: `kernel` = 2 / 4 below M = 2048 selects a 256x256 kernel where it reports the 128x128 kernel's N / 8 columns).
+ * Both refusals come before anything is launched. */
 #define CSMOE_KERNEL_AUTO 0
 #define CSMOE_KERNEL_GENERIC 1
 #define CSMOE_KERNEL_V2 2

@@ -58,7 +58,8 @@ def test_rowspace_fuzz(i, E, M, N, Kd, b_layout, epi, act, kern):
     res = ops.grouped_gemm(A, ops.ptr_array(Bs, DEV), b_layout, Bs[0].stride(0), N, off.to(DEV), E, **kw)
     c, c2 = res if epi == 2 else (res, None)
     if kern == 0 and Kd % 128 == 0:
-        # the two 256x256 kernels are independent implementations of the same sums, rounded at the same points: bit-identical
+        # the two 256x256 kernels are independent implementations of the same sums, rounded at the same points; on this random data
+        # the test asserts agreement within 2^-7 of the largest output (bit identity on exact data: test_gemm_conformance_gpu.py)
         r2 = ops.grouped_gemm(A, ops.ptr_array(Bs, DEV), b_layout, Bs[0].stride(0), N, off.to(DEV), E, **{**kw, "kernel": 2})
         r4 = ops.grouped_gemm(A, ops.ptr_array(Bs, DEV), b_layout, Bs[0].stride(0), N, off.to(DEV), E, **{**kw, "kernel": 4})
         for a_, b_ in zip(r2 if epi == 2 else (r2,), r4 if epi == 2 else (r4,)):
