@@ -64,6 +64,8 @@ int k_gate_select_rows();
 int k_gate_select(const void*, const void*, int, int, int, int, int, int, float, void*, float*, int32_t*, float*, int32_t*, hipStream_t);
 int k_dispatch_rows(const void*, const int32_t*, int, void*, int, int, int, hipStream_t);
 int k_dispatch_tokens(const void*, const int32_t*, int, void*, int, int, int, hipStream_t);
+int k_dispatch_quant_mxfp8(const void* x, const int32_t* index, int K, void* xs, void* q, void* s, int n, int D, int tokens,
+                           hipStream_t st);
 int k_combine(const void*, const int32_t*, const int32_t*, const float*, const void*, const void*, void*, int, int, int, int, int,
               hipStream_t, const void* pre);
 int k_combine_bwd(const void*, const void*, const int32_t*, const float*, void*, float*, int, int, int, int, int, hipStream_t);
@@ -274,6 +276,32 @@ int csmoe_dispatch_tokens(const void* x, const int32_t* slot_of, int K, void* xs
   CSMOE_CHECK_ARG(dtype_ok(dtype) && K > 0 && T >= 0 && D > 0, "dispatch_tokens: bad arguments");
   CSMOE_CHECK_ARG(T == 0 || (x && slot_of && xs), "dispatch_tokens: null pointer");
   return k_dispatch_tokens(x, slot_of, K, xs, T, D * esize(dtype), csmoe_dispatch_vec_ok(x, xs, D, dtype), (hipStream_t)stream);
+}
+
+// the gather and the MXFP8 row quantiser in one pass (fp8_quant.hip); bf16 rows of whole 32-element blocks, 16-byte aligned
+static int dispatch_quant_args(const char* who, const void* x, const int32_t* index, int K, const void* xs, const uint8_t* q,
+                               const uint8_t* s, int n, int D, int dtype) {
+  CSMOE_CHECK_ARG(dtype == CSMOE_BF16, "%s: bad dtype %d (bf16 rows only)", who, dtype);
+  CSMOE_CHECK_ARG(K > 0 && n >= 0 && D > 0, "%s: bad shape K=%d rows=%d D=%d", who, K, n, D);
+  CSMOE_CHECK_ARG(D % 32 == 0, "%s: needs D %% 32 == 0 (D=%d)", who, D);
+  if (n == 0) return CSMOE_OK;
+  CSMOE_CHECK_ARG(q && s, "%s: null q / s", who);
+  CSMOE_CHECK_ARG(x && index, "%s: null x or index", who);
+  CSMOE_CHECK_ARG((((uintptr_t)x | (uintptr_t)xs) & 15) == 0 && ((uintptr_t)q & 7) == 0, "%s: x / xs must be 16-byte and q 8-byte aligned",
+                  who);
+  return CSMOE_OK;
+}
+
+int csmoe_dispatch_rows_mxfp8(const void* x, const int32_t* perm, int K, void* xs, uint8_t* q, uint8_t* s, int n, int D, int dtype,
+                              csmoe_stream_t stream) {
+  if (int rc = dispatch_quant_args("dispatch_rows_mxfp8", x, perm, K, xs, q, s, n, D, dtype)) return rc;
+  return k_dispatch_quant_mxfp8(x, perm, K, xs, q, s, n, D, 0, (hipStream_t)stream);
+}
+
+int csmoe_dispatch_tokens_mxfp8(const void* x, const int32_t* slot_of, int K, void* xs, uint8_t* q, uint8_t* s, int T, int D, int dtype,
+                                csmoe_stream_t stream) {
+  if (int rc = dispatch_quant_args("dispatch_tokens_mxfp8", x, slot_of, K, xs, q, s, T, D, dtype)) return rc;
+  return k_dispatch_quant_mxfp8(x, slot_of, K, xs, q, s, T, D, 1, (hipStream_t)stream);
 }
 
 int csmoe_dispatch_rows_bwd(const void* dxs, const int32_t* slot_of, int K, const void* add, void* dx, int T, int D, int dtype,

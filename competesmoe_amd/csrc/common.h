@@ -37,6 +37,12 @@ void csmoe_set_error(const char* fmt, ...);
     }                                                                                \
   } while (0)
 
+// grid-stride row kernels: 4 rows (waves) per workgroup; caps of 2048..16384 workgroups measure the same (tools/hbm_bench.py)
+inline int stride_grid(int rows) {
+  const int g = (rows + 3) / 4;
+  return g < 1 ? 1 : (g > 4096 ? 4096 : g);
+}
+
 // ------------------------------------------------------------------ dtype helpers (device)
 template <typename T> struct DT;
 template <> struct DT<float> {

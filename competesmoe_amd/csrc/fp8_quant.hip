@@ -341,6 +341,76 @@ __global__ void __launch_bounds__(256) quant_tokens_kernel(const bf16* x, int64_
   }
 }
 
+
+// ---- gather rows into the binned row space AND quantise them, one pass (csmoe_dispatch_rows_mxfp8 / csmoe_dispatch_tokens_mxfp8) ----
+// moe_kernels.hip's dispatch kernels followed by quant_rows_kernel write every gathered bf16 row and read it straight back; here the
+// row is quantised from the registers that hold it for the copy.  One wave per source row, eight 16-byte loads in flight per lane (one
+// 8 KiB row per pass).  A 32-element block is the 16-byte pieces of four consecutive lanes: the block amax is two cross-lane steps
+// (xor 1, xor 2; fmaxf drops a NaN operand, so the order of the maxima does not matter and the result is quant_rows_kernel's), every
+// lane converts its 8 values and stores 8 bytes, one lane in four stores the scale byte.  D % 32 == 0 makes the pieces of a row a
+// multiple of 4, so a quad is in range or out of range as a whole.  TOKENS: the wave's row is token t, stored to its K binned rows
+// slot_of[t*K + k] (read and quantised once); else destination row m takes source row perm[m] / K.  xs may be null (no bf16 copy).
+#ifndef CSMOE_DQ_LOADS
+#define CSMOE_DQ_LOADS 8
+#endif
+constexpr int DQ_LOADS = CSMOE_DQ_LOADS;      // 16-byte loads in flight per lane
+template <bool TOKENS>
+__global__ void __launch_bounds__(256) dispatch_quant_kernel(const bf16* x, const int32_t* index, int K, bf16* xs, uint8_t* q,
+                                                             uint8_t* s, int n, int D) {
+  const int lane = threadIdx.x & 63;
+  const int wave_g = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int nw = gridDim.x * 4;
+  const int nv = D >> 3;                    // 16-byte pieces (8 bf16) per row
+  const int nb = D >> 5;                    // scale bytes per row
+  for (int r = wave_g; r < n; r += nw) {
+    const int64_t srow = TOKENS ? r : index[r] / K;
+    const bf16x8* src = (const bf16x8*)(x + srow * D);
+    for (int c0 = 0; c0 < nv; c0 += 64 * DQ_LOADS) {
+      bf16x8 v[DQ_LOADS];
+#pragma unroll
+      for (int c = 0; c < DQ_LOADS; ++c) {
+        const int i = c0 + c * 64 + lane;
+        if (i < nv) v[c] = src[i];
+      }
+      u32x2 o[DQ_LOADS];
+      int sb[DQ_LOADS];
+#pragma unroll
+      for (int c = 0; c < DQ_LOADS; ++c) {
+        const bool live = c0 + c * 64 + lane < nv;
+        float f[8];
+        float amax = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          f[j] = live ? (float)v[c][j] : 0.f;
+          amax = fmaxf(amax, fabsf(f[j]));
+        }
+        amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+        amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+        sb[c] = e8m0_of_amax(amax);
+        const float inv = inv_scale_of(sb[c]);
+        o[c][0] = pack4_e4m3(f[0] * inv, f[1] * inv, f[2] * inv, f[3] * inv);
+        o[c][1] = pack4_e4m3(f[4] * inv, f[5] * inv, f[6] * inv, f[7] * inv);
+      }
+      const int reps = TOKENS ? K : 1;
+      for (int k = 0; k < reps; ++k) {
+        const int64_t m = TOKENS ? index[(int64_t)r * K + k] : r;
+        bf16x8* dst = xs ? (bf16x8*)(xs + m * D) : nullptr;
+        u32x2* qd = (u32x2*)(q + m * D);
+        uint8_t* sd = s + m * nb;
+#pragma unroll
+        for (int c = 0; c < DQ_LOADS; ++c) {
+          const int i = c0 + c * 64 + lane;
+          if (i < nv) {
+            if (dst) dst[i] = v[c];
+            qd[i] = o[c];
+            if ((lane & 3) == 0) sd[i >> 2] = (uint8_t)sb[c];
+          }
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 int k_quantize_mxfp8_both(const void* const* x_ptrs, const void* x_single, int E, int64_t ldx, int R, int C, int in_dtype, void* q,
@@ -398,5 +468,21 @@ int k_quantize_mxfp8_tokens(const void* x, int64_t ldx, const int32_t* offsets, 
     hipLaunchKernelGGL((quant_tokens_kernel<false>), grid, block, 0, stream, (const bf16*)x, ldx, offsets, (const int32_t*)poff, E, C,
                        n_pad, (uint8_t*)q, (uint8_t*)s, (uint8_t*)qt, (uint8_t*)st);
   CSMOE_CHECK_LAUNCH("quantize_mxfp8_tokens");
+  return CSMOE_OK;
+}
+
+// index = perm [n] (rows form: source row perm[m] / K) or slot_of [n * K] (tokens form: n tokens); bounds are the caller's contract,
+// as for k_dispatch_rows / k_dispatch_tokens
+int k_dispatch_quant_mxfp8(const void* x, const int32_t* index, int K, void* xs, void* q, void* s, int n, int D, int tokens,
+                           hipStream_t st) {
+  if (n == 0) return CSMOE_OK;
+  dim3 grid(stride_grid(n)), block(256);
+  if (tokens)
+    hipLaunchKernelGGL((dispatch_quant_kernel<true>), grid, block, 0, st, (const bf16*)x, index, K, (bf16*)xs, (uint8_t*)q, (uint8_t*)s,
+                       n, D);
+  else
+    hipLaunchKernelGGL((dispatch_quant_kernel<false>), grid, block, 0, st, (const bf16*)x, index, K, (bf16*)xs, (uint8_t*)q, (uint8_t*)s,
+                       n, D);
+  CSMOE_CHECK_LAUNCH(tokens ? "dispatch_tokens_mxfp8" : "dispatch_rows_mxfp8");
   return CSMOE_OK;
 }

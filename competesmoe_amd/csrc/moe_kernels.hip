@@ -1159,9 +1159,6 @@ __global__ void __launch_bounds__(256) expert_order_kernel(const int32_t* offset
   }
 }
 
-// grid-stride row kernels: 4 rows (waves) per workgroup; caps of 2048..16384 workgroups measure the same (tools/hbm_bench.py)
-inline int stride_grid(int rows) { return std::max(1, std::min((rows + 3) / 4, 4096)); }
-
 // combine backward for K == 2, bf16 rows, D a multiple of 512: the upstream-gradient chunk and both y chunks of four 8-column
 // chunks (12 loads) are in flight per lane before the first store; same per-lane accumulation order of the dot products as the
 // generic kernel (bit-identical dw).

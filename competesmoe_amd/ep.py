@@ -495,6 +495,15 @@ class _Lane:
             return r
         return r[self.lb.perm.long()] if r.shape[1] == 1 else ops.dispatch_rows(r, self.lb)
 
+    def arrived_mxfp8(self, r: torch.Tensor):
+        """A waited-for receive buffer of bf16 rows as (expert-major rows, their MXFP8 elements, scales): the regroup pass quantises
+        the rows it moves (ops.dispatch_rows_mxfp8); rows that landed expert-major are quantised where they are."""
+        if r.shape[0] == 0:
+            return r, r.new_empty(0, r.shape[1], dtype=torch.uint8), r.new_empty(0, r.shape[1] // 32, dtype=torch.uint8)
+        if self.as_is:
+            return (r,) + ops.quantize_mxfp8(r)
+        return ops.dispatch_rows_mxfp8(r, self.lb)
+
     def give_back(self, rows: torch.Tensor, dst: torch.Tensor):
         """owners -> token side, asynchronously, into the binned row space `dst`: (handle, buffer to keep alive until waited for)."""
         cp = self.cp
@@ -519,13 +528,20 @@ class EPFFNPacked(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x2, w, idx, keys, values, bias, o_bias, act: int, combine_mode: int, E_global: int, group, chunks: int,
-                direct: bool, residual=None, stats=None):
+                direct: bool, residual=None, stats=None, x_shared=None, keys_shared=None, values_shared=None, bias_shared=None):
+        """`x_shared`, `keys_shared` [D, Fs], `values_shared` [Fs, Dout], `bias_shared` [Fs] or None: the always-on shared expert of
+        the deepseek layers (functional.DenseFFN's body), launched after every lane's send is queued and before the first wait, in the
+        forward and in the backward; its output enters the combine epilogue as the residual (the bits of `out + out_shared`), its dx
+        is returned as the gradient of `x_shared`, a separate input."""
         from . import functional as Fn
         x2 = x2.contiguous()
         op = x2.dtype
         if op == torch.bfloat16:
             w = w.to(op).float()
         El, D, F = keys.shape
+        has_shared = x_shared is not None
+        # the shared output takes the residual slot of the combine: no block residual may arrive with it (_fuses_residual = False)
+        assert not (has_shared and residual is not None), "EPFFNPacked: a shared expert and a block residual share one combine slot"
         Dout = values.shape[2]
         dev = x2.device
         T = x2.shape[0]
@@ -572,6 +588,10 @@ class EPFFNPacked(torch.autograd.Function):
         plan = make_plan(bins.counts, group, per_expert=True)
         lanes = [_Lane(plan, cp, direct, group) for cp in chunk_plan(plan, chunks)]
         sent = [ln.send(xs) for ln in lanes]               # every outbound exchange is queued now, on the process group's stream
+        ctx.shared = None
+        if has_shared:                                     # no communication: its GEMMs cover the exchange
+            residual, sh_saved, sh_cfg = Fn.dense_ffn_forward(x_shared, keys_shared, bias_shared, values_shared, None, act, L.B_KN)
+            ctx.shared = (sh_saved, sh_cfg)
         y = torch.empty(bins.n, Dout, dtype=op, device=dev)
         back, saved = [], []
         for ln, (r, wk) in zip(lanes, sent):
@@ -606,7 +626,7 @@ class EPFFNPacked(torch.autograd.Function):
         ctx.tab, ctx.w, ctx.group, ctx.op = tab, w, group, op
         ctx.saved = (bins, lanes, saved, y)
         ctx.keep = (k_op, v_op, b_op)
-        ctx.has = (bias is not None, o_bias is not None, residual is not None)
+        ctx.has = (bias is not None, o_bias is not None, residual is not None and not has_shared)
         ctx.bias_dtype = None if bias is None else bias.dtype
         ctx.ob_dtype = None if o_bias is None else o_bias.dtype
         return out
@@ -646,6 +666,13 @@ class EPFFNPacked(torch.autograd.Function):
         else:
             sent = [(ln.send(dy), None) for ln in lanes]
         extra_sent = [ln.send(dy_extra) for ln in lanes] if dy_extra is not None else [None] * len(lanes)
+        sh = (None,) * 4
+        if ctx.shared is not None:                       # the shared expert's backward, between the sends and the first wait
+            sh_saved, sh_cfg = ctx.shared
+            ctx.shared = None
+            need = ctx.needs_input_grad
+            dx_s, gks, gbs, gvs, _ = Fn.dense_ffn_backward(sh_saved, sh_cfg, dout, (need[15], need[16], need[18], need[17], False))
+            sh = (dx_s, gks, gvs, gbs)
         gk = gv = gb = None
         if need_params:
             es = torch.tensor([], dtype=pd).element_size()
@@ -721,7 +748,141 @@ class EPFFNPacked(torch.autograd.Function):
         if ctx.has[1] and ctx.needs_input_grad[6]:
             gob = Fn._chunked_dense_colsum(dout, ctx.ob_dtype)
         return (dx2, dw, None, gk, gv, gb, gob, None, None, None, None, None, None,
-                dout if (ctx.has[2] and ctx.needs_input_grad[13]) else None, None)
+                dout if (ctx.has[2] and ctx.needs_input_grad[13]) else None, None, *sh)
+
+
+class EPFFNPackedFP8(torch.autograd.Function):
+    """functional.MoEFFNPackedFP8 (the four row-space expert GEMMs of a step on the block-scaled fp8 pipe, BASELINE config 5) with the
+    packed experts sharded over the group, row for row, on the lanes of EPFFNPacked.  bf16 rows travel (the owners need them for the
+    bf16 weight gradients); the owners' regroup pass quantises them as it moves them (_Lane.arrived_mxfp8).  The master weights of
+    the local shard are quantised once per forward (or per parameter version with `cache`) and sliced per lane; the backward pair is
+    kept.  Backward: combine_bwd on the token side as on one GPU -- dy = round(w * dout row) travels, one message per lane, and d w
+    comes from the returned y; there is no weight or dot column (the fp8 layer scales before the product).  Every rank takes the same
+    road through every collective: nothing here branches on a row count in a way that changes the messages.
+    `x_shared` ...: the shared expert (functional.DenseFFNFP8's body) between the sends and the first wait, as in EPFFNPacked."""
+
+    @staticmethod
+    def forward(ctx, x2, w, idx, keys, values, bias, act: int, combine_mode: int, E_global: int, group, chunks: int, direct: bool,
+                cache: bool = False, x_shared=None, keys_shared=None, values_shared=None, bias_shared=None):
+        from . import functional as Fn
+        x2 = x2.contiguous()
+        if x2.dtype != torch.bfloat16:
+            raise ValueError("competesmoe_amd: the fp8 expert path takes bf16 activations (run under bf16 autocast)")
+        w = w.to(torch.bfloat16).float()          # the K weights enter as bf16 values; d w comes back unrounded
+        El, D, F = keys.shape
+        Dout = values.shape[2]
+        T = x2.shape[0]
+        dev = x2.device
+        bins = ops.bin_tokens(idx, E_global)
+        xs = ops.dispatch_tokens(x2, bins)
+        plan = make_plan(bins.counts, group, per_expert=True)
+        lanes = [_Lane(plan, cp, direct, group) for cp in chunk_plan(plan, chunks)]
+        sent = [ln.send(xs) for ln in lanes]               # every outbound exchange is queued now, on the process group's stream
+        y_shared = None
+        ctx.shared = None
+        if x_shared is not None:                           # no communication: its GEMMs cover the exchange
+            y_shared, sh_saved, sh_cfg = Fn.dense_ffn_fp8_forward(x_shared, keys_shared, bias_shared, values_shared, act, cache)
+            ctx.shared = (sh_saved, sh_cfg)
+        (kq_b, ks_b), (kq, ks) = Fn._quantize_weight_both(keys, cache)        # backward pair [El, D, F]; forward pair [El, F, D]
+        (vq_b, vs_b), (vq, vs) = Fn._quantize_weight_both(values, cache)      # backward pair [El, F, Dout]; forward pair [El, Dout, F]
+        b_op = b1 = None
+        if bias is not None:
+            b_op = bias.to(torch.bfloat16).contiguous()
+            b1 = ops.ptr_table(b_op, El, F * 2)
+        y = torch.empty(bins.n, Dout, dtype=torch.bfloat16, device=dev)
+        back, saved = [], []
+        for ln, (r, wk) in zip(lanes, sent):
+            with ops._timed("ep_wait_exposed"):
+                wk.wait()
+            e0, e1 = ln.cp.e0, ln.cp.e1
+            rs, rq, rsc = ln.arrived_mxfp8(r)              # the bf16 rows are kept for the `keys` gradient
+            lb = ln.lb
+            hpre, hact = ops.grouped_gemm_mxfp8(rq, rsc, kq[e0:e1], ks[e0:e1], lb.offsets, bias_ptrs=None if b1 is None else b1[e0:e1],
+                                                epilogue=L.EPI_BIAS_ACT, act=act, want_c2=True, want_c=act != L.ACT_RELU)
+            del rq, rsc
+            hq, hs = _quantize_rows(hact)
+            ys = ops.grouped_gemm_mxfp8(hq, hs, vq[e0:e1], vs[e0:e1], lb.offsets)
+            back.append(ln.give_back(ys, y))
+            saved.append((rs, hpre, hact))
+        with ops._timed("ep_wait_exposed"):
+            for wk, _ in back:
+                wk.wait()
+        del back, sent
+        out = ops.combine(y, bins, idx, w, combine_mode, T, residual=y_shared)
+        ctx.saved = (bins, lanes, saved, y, b_op)
+        ctx.wq = (kq_b, ks_b, vq_b, vs_b)
+        ctx.w, ctx.shape, ctx.pd = w, (El, D, F, Dout), keys.dtype
+        ctx.cfg = (act, None if bias is None else bias.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import functional as Fn
+        if ctx.saved is None:
+            raise RuntimeError("competesmoe_amd: saved activations were freed by the first backward pass; run the forward again")
+        bins, lanes, saved, y, _ = ctx.saved
+        ctx.saved = None
+        act, bias_dtype = ctx.cfg
+        El, D, F, Dout = ctx.shape
+        pd = ctx.pd
+        dev = dout.device
+        T = dout.shape[0]
+        need = ctx.needs_input_grad
+        need_dx, need_dw = need[0], need[1]
+        need_params = need[3] or need[4] or need[5]
+        dout = dout.contiguous()
+        dy, dw = ops.combine_bwd(dout, y if need_dw else None, bins, ctx.w, want_dw=need_dw, act_dtype=torch.bfloat16)
+        del y
+        sent = [ln.send(dy) for ln in lanes]
+        sh = (None,) * 4
+        if ctx.shared is not None:                       # the shared expert's backward, between the sends and the first wait
+            sh_saved, sh_cfg = ctx.shared
+            ctx.shared = None
+            dx_s, gks, gbs, gvs = Fn.dense_ffn_fp8_backward(sh_saved, sh_cfg, dout, (need[13], need[14], need[16], need[15]))
+            sh = (dx_s, gks, gvs, gbs)
+        kq, ks, vq, vs = ctx.wq
+        ctx.wq = None
+        gk = gv = gb = None
+        if need_params:
+            es = torch.tensor([], dtype=pd).element_size()
+            gk = torch.empty(El, D, F, dtype=pd, device=dev)
+            gv = torch.empty(El, F, Dout, dtype=pd, device=dev)
+            tk, tv = ops.ptr_table(gk, El, D * F * es), ops.ptr_table(gv, El, F * Dout * es)
+            if bias_dtype is not None:
+                gb = torch.empty(El, F, dtype=bias_dtype, device=dev)
+        dxs = torch.empty(bins.n, D, dtype=torch.bfloat16, device=dev) if need_dx else None
+        back = []
+        for ln, (r, wk), (rs, hpre, hact) in zip(lanes, sent, saved):
+            with ops._timed("ep_wait_exposed"):
+                wk.wait()
+            e0, e1 = ln.cp.e0, ln.cp.e1
+            Ec, lb = e1 - e0, ln.lb
+            dys, dyq, dysc = ln.arrived_mxfp8(r)           # the bf16 dy is kept for the `values` gradient
+            dh = ops.grouped_gemm_mxfp8(dyq, dysc, vq[e0:e1], vs[e0:e1], lb.offsets, epilogue=L.EPI_ACTGRAD, act=act,     # values as stored
+                                        aux=hpre if hpre is not None else hact)
+            del dyq, dysc
+            if need_dx:                                  # input gradient first: its return trip overlaps this group's weight gradients
+                dhq, dhs = _quantize_rows(dh)
+                back.append(ln.give_back(ops.grouped_gemm_mxfp8(dhq, dhs, kq[e0:e1], ks[e0:e1], lb.offsets), dxs))   # dxs = dh @ keys[e]^T
+                del dhq, dhs
+            if need_params:
+                ops.grouped_wgrad(hact, dys, lb.offsets, Ec, gv, tv[e0:e1], xcd_order=lb.xcd_order)
+                ops.grouped_wgrad(rs, dh, lb.offsets, Ec, gk, tk[e0:e1], xcd_order=lb.xcd_order)
+                if gb is not None:
+                    gb[e0:e1] = _grouped_colsum(dh, lb.offsets, Ec, bias_dtype)
+        with ops._timed("ep_wait_exposed"):
+            for wk, _ in back:
+                wk.wait()
+        del back, sent
+        dx2 = ops.dispatch_rows_bwd(dxs, bins, T) if need_dx else None
+        return (dx2, dw, None, gk, gv, gb, None, None, None, None, None, None, None, *sh)
+
+
+def _quantize_rows(t: torch.Tensor):
+    """ops.quantize_mxfp8 of [n, C] rows; a lane that holds no rows launches nothing."""
+    if t.shape[0] == 0:
+        return t.new_empty(0, t.shape[1], dtype=torch.uint8), t.new_empty(0, t.shape[1] // 32, dtype=torch.uint8)
+    return ops.quantize_mxfp8(t)
 
 
 class EPFFNPackedSlots(torch.autograd.Function):
@@ -750,7 +911,7 @@ class EPFFNPackedSlots(torch.autograd.Function):
             extra = ops.dispatch_rows(dy_tk.reshape(bins.n, -1).to(ctx.op).contiguous(), _SlotMap(bins.perm, bins.n))
         if dout is None:
             dout = torch.zeros(ctx.w.shape[0], ctx.tab.Dout, dtype=ctx.op, device=ctx.w.device)
-        return EPFFNPacked._backward(ctx, dout, extra)
+        return EPFFNPacked._backward(ctx, dout, extra)[:15]     # this function takes no shared expert
 
 
 # default of the local competition pass's dX chain, read once per process: 1 = every expert after the first adds its dX product into the

@@ -865,6 +865,58 @@ class MoEFFNPackedSlots(torch.autograd.Function):
 
 
 # ======================================================================================================== dense FFN
+def dense_ffn_forward(x2, w1, b1, w2, b2, act: int, layout: int):
+    """The body of DenseFFN.forward: (y, tensors its backward needs, cfg).  Also called by the expert-parallel functions (ep.py), which
+    run the shared expert between their sends and their first wait."""
+    x2 = x2.contiguous()
+    op = x2.dtype
+
+    def cast(t):
+        if t is None:
+            return None
+        if t.dtype == op:
+            return t.contiguous()
+        if _WEIGHT_CACHE_ON and t._base is None:      # fresh slices (keys[e]) die with the call: their entries could never hit
+            c, hit = _cached_copy(t, op)
+            if not hit:
+                c = t.to(op)
+                _remember(t, op, c)
+            return c
+        return t.to(op)
+
+    epi1 = L.EPI_BIAS_ACT
+    if b1 is not None and b1.dtype == torch.float32 and op == torch.bfloat16 and layout == L.B_KN:
+        # the pretrain stack's shared expert: cvmm output + fp32 master bias (see MoEFFNPacked)
+        w1o, b1o, w2o, b2o = cast(w1), b1.contiguous(), cast(w2), cast(b2)
+        epi1 = L.EPI_ROUND_BIAS32_ACT
+    else:
+        w1o, b1o, w2o, b2o = cast(w1), cast(b1), cast(w2), cast(b2)
+    hpre, hact = ops.dense_gemm(x2, w1o, layout, bias=b1o, epilogue=epi1, act=act, want_c2=True, want_c=act != L.ACT_RELU)
+    y = ops.dense_gemm(hact, w2o, layout, bias=b2o, epilogue=L.EPI_BIAS if b2o is not None else L.EPI_PLAIN)
+    cfg = (act, layout, w1.dtype, None if b1 is None else b1.dtype, w2.dtype, None if b2 is None else b2.dtype)
+    return y, (x2, w1o, w2o, hpre, hact), cfg
+
+
+def dense_ffn_backward(saved, cfg, dy, needs):
+    """The body of DenseFFN.backward: (dx, gw1, gb1, gw2, gb2); `needs` = which of (x2, w1, b1, w2, b2) take a gradient."""
+    x2, w1o, w2o, hpre, hact = saved
+    act, layout, dt_w1, dt_b1, dt_w2, dt_b2 = cfg
+    dy = dy.contiguous()
+    dh = ops.dense_gemm(dy, w2o, _flip(layout), epilogue=L.EPI_ACTGRAD, act=act, aux=hpre if hpre is not None else hact)
+    gw1 = gb1 = gw2 = gb2 = dx = None
+    if needs[3]:
+        gw2 = _dense_wgrad(dy, hact, dt_w2) if layout == L.B_NK else _dense_wgrad(hact, dy, dt_w2)
+    if dt_b2 is not None and needs[4]:
+        gb2 = _chunked_dense_colsum(dy, dt_b2)
+    if needs[1]:
+        gw1 = _dense_wgrad(dh, x2, dt_w1) if layout == L.B_NK else _dense_wgrad(x2, dh, dt_w1)
+    if dt_b1 is not None and needs[2]:
+        gb1 = _chunked_dense_colsum(dh, dt_b1)
+    if needs[0]:
+        dx = ops.dense_gemm(dh, w1o, _flip(layout))
+    return dx, gw1, gb1, gw2, gb2
+
+
 class DenseFFN(torch.autograd.Function):
     """One always-on expert over all tokens: Linear(+b) -> act -> Linear(+b).  The shared expert of `smoe_share` /
     `deepseekv3` (moe_model/model/moe/shard_smoe.py:53, deepseekv3.py:44), the pretrain shared cvmm with an all-zero
@@ -872,52 +924,15 @@ class DenseFFN(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x2, w1, b1, w2, b2, act: int, layout: int):
-        x2 = x2.contiguous()
-        op = x2.dtype
-        def cast(t):
-            if t is None:
-                return None
-            if t.dtype == op:
-                return t.contiguous()
-            if _WEIGHT_CACHE_ON and t._base is None:      # fresh slices (keys[e]) die with the call: their entries could never hit
-                c, hit = _cached_copy(t, op)
-                if not hit:
-                    c = t.to(op)
-                    _remember(t, op, c)
-                return c
-            return t.to(op)
-
-        epi1 = L.EPI_BIAS_ACT
-        if b1 is not None and b1.dtype == torch.float32 and op == torch.bfloat16 and layout == L.B_KN:
-            # the pretrain stack's shared expert: cvmm output + fp32 master bias (see MoEFFNPacked)
-            w1o, b1o, w2o, b2o = cast(w1), b1.contiguous(), cast(w2), cast(b2)
-            epi1 = L.EPI_ROUND_BIAS32_ACT
-        else:
-            w1o, b1o, w2o, b2o = cast(w1), cast(b1), cast(w2), cast(b2)
-        hpre, hact = ops.dense_gemm(x2, w1o, layout, bias=b1o, epilogue=epi1, act=act, want_c2=True, want_c=act != L.ACT_RELU)
-        y = ops.dense_gemm(hact, w2o, layout, bias=b2o, epilogue=L.EPI_BIAS if b2o is not None else L.EPI_PLAIN)
-        ctx.save_for_backward(x2, w1o, w2o, hpre, hact)
-        ctx.cfg = (act, layout, w1.dtype, None if b1 is None else b1.dtype, w2.dtype, None if b2 is None else b2.dtype)
+        y, saved, ctx.cfg = dense_ffn_forward(x2, w1, b1, w2, b2, act, layout)
+        ctx.save_for_backward(*saved)
         ctx.handoff = _take_handoff()
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x2, w1o, w2o, hpre, hact = ctx.saved_tensors
-        act, layout, dt_w1, dt_b1, dt_w2, dt_b2 = ctx.cfg
-        dy = dy.contiguous()
-        dh = ops.dense_gemm(dy, w2o, _flip(layout), epilogue=L.EPI_ACTGRAD, act=act, aux=hpre if hpre is not None else hact)
-        gw1 = gb1 = gw2 = gb2 = dx = None
-        if ctx.needs_input_grad[3]:
-            gw2 = _dense_wgrad(dy, hact, dt_w2) if layout == L.B_NK else _dense_wgrad(hact, dy, dt_w2)
-        if dt_b2 is not None and ctx.needs_input_grad[4]:
-            gb2 = _chunked_dense_colsum(dy, dt_b2)
-        if ctx.needs_input_grad[1]:
-            gw1 = _dense_wgrad(dh, x2, dt_w1) if layout == L.B_NK else _dense_wgrad(x2, dh, dt_w1)
-        if dt_b1 is not None and ctx.needs_input_grad[2]:
-            gb1 = _chunked_dense_colsum(dh, dt_b1)
-        if ctx.needs_input_grad[0]:
-            dx = ops.dense_gemm(dh, w1o, _flip(layout))
+        dx, gw1, gb1, gw2, gb2 = dense_ffn_backward(ctx.saved_tensors, ctx.cfg, dy, ctx.needs_input_grad[:5])
+        if dx is not None:
             h = ctx.handoff
             if h is not None and h.has_consumer and not h.routed_done:
                 # the always-on expert of a shared-expert layer: its dx is the FIRST addend of the routed step's chain (DxHandoff);
@@ -1181,8 +1196,7 @@ class MoEFFNPackedFP8(torch.autograd.Function):
         E, D, F = keys.shape
         T = x2.shape[0]
         bins = ops.bin_tokens(idx, E)
-        xs = ops.dispatch_tokens(x2, bins)
-        xq, xsc = ops.quantize_mxfp8(xs)
+        xs, xq, xsc = ops.dispatch_tokens_mxfp8(x2, bins)       # the gather and the quantiser in one pass (CSMOE_DISPATCH_QUANT=0: two)
         (kq_b, ks_b), (kq, ks) = _quantize_weight_both(keys, cache)        # backward pair [E, D, F]; forward pair [E, F, D] (reduction over D)
         b_op = b1 = None
         if bias is not None:
@@ -1263,58 +1277,68 @@ class DenseFFNFP8(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x2, w1, b1, w2, act: int, cache: bool = False, wgrad_fp8: bool = False):
-        x2 = x2.contiguous()
-        xq, xsc = ops.quantize_mxfp8(x2)
-        (w1q_b, w1s_b), (w1q, w1s) = _quantize_weight_both(w1, cache)      # backward pair [D, Fs]; forward pair [Fs, D]
-        b1o = None if b1 is None else b1.to(torch.bfloat16).contiguous()
-        hpre, hact = ops.dense_gemm_mxfp8(xq, xsc, w1q, w1s, bias=b1o, epilogue=L.EPI_BIAS_ACT, act=act, want_c2=True,
-                                          want_c=act != L.ACT_RELU)
-        hq, hs = ops.quantize_mxfp8(hact)
-        (w2q_b, w2s_b), (w2q, w2s) = _quantize_weight_both(w2, cache)      # backward pair [Fs, Dout]; forward pair [Dout, Fs]
-        y = ops.dense_gemm_mxfp8(hq, hs, w2q, w2s)
-        ctx.save_for_backward(x2, hpre, hact, w1, w2, w1q_b, w1s_b, w2q_b, w2s_b)
-        ctx.cfg = (act, None if b1 is None else b1.dtype)
+        y, saved, ctx.cfg = dense_ffn_fp8_forward(x2, w1, b1, w2, act, cache)
+        ctx.save_for_backward(*saved)
         ctx.wgrad_fp8 = bool(wgrad_fp8)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x2, hpre, hact, w1, w2, w1q, w1s, w2q, w2s = ctx.saved_tensors
-        act, b1_dtype = ctx.cfg
-        dy = dy.contiguous()
-        f8w = ctx.wgrad_fp8
-        T = dy.shape[0]
-        if f8w and ctx.needs_input_grad[3]:
-            off = ops.dense_offsets(T, dy.device)
-            (dyt, dyts, poff), (dyq, dys) = ops.quantize_mxfp8_tokens(dy, off, 1, rows=True)
-        else:
-            dyq, dys = ops.quantize_mxfp8(dy)
-        dh = ops.dense_gemm_mxfp8(dyq, dys, w2q, w2s, epilogue=L.EPI_ACTGRAD, act=act, aux=hpre if hpre is not None else hact)
-        gw1 = gb1 = gw2 = dx = None
-        if ctx.needs_input_grad[3]:
-            if f8w:
-                ht, hts, _ = ops.quantize_mxfp8_tokens(hact, off, 1)
-                gw2 = _dense_wgrad_fp8(ht, hts, dyt, dyts, poff, T, w2.dtype)     # [Fs, Dout]
-                del ht, hts, dyt, dyts
-            else:
-                gw2 = _dense_wgrad(hact, dy, w2.dtype)                     # [Fs, Dout]
-        dhq = dhs = None
-        if ctx.needs_input_grad[1]:
-            if f8w:
-                off = ops.dense_offsets(T, dy.device)
-                xt, xts, poff = ops.quantize_mxfp8_tokens(x2, off, 1)
-                if ctx.needs_input_grad[0]:
-                    (dht, dhts, _), (dhq, dhs) = ops.quantize_mxfp8_tokens(dh, off, 1, rows=True)
-                else:
-                    dht, dhts, _ = ops.quantize_mxfp8_tokens(dh, off, 1)
-                gw1 = _dense_wgrad_fp8(xt, xts, dht, dhts, poff, T, w1.dtype)    # [D, Fs]
-                del xt, xts, dht, dhts
-            else:
-                gw1 = _dense_wgrad(x2, dh, w1.dtype)                       # [D, Fs]
-        if b1_dtype is not None and ctx.needs_input_grad[2]:
-            gb1 = _chunked_dense_colsum(dh, b1_dtype)
-        if ctx.needs_input_grad[0]:
-            if dhq is None:
-                dhq, dhs = ops.quantize_mxfp8(dh)
-            dx = ops.dense_gemm_mxfp8(dhq, dhs, w1q, w1s)
+        dx, gw1, gb1, gw2 = dense_ffn_fp8_backward(ctx.saved_tensors, ctx.cfg, dy, ctx.needs_input_grad[:4], ctx.wgrad_fp8)
         return dx, gw1, gb1, gw2, None, None, None
+
+
+def dense_ffn_fp8_forward(x2, w1, b1, w2, act: int, cache: bool):
+    """The body of DenseFFNFP8.forward: (y, tensors its backward needs, cfg); also called by ep.EPFFNPackedFP8."""
+    x2 = x2.contiguous()
+    xq, xsc = ops.quantize_mxfp8(x2)
+    (w1q_b, w1s_b), (w1q, w1s) = _quantize_weight_both(w1, cache)      # backward pair [D, Fs]; forward pair [Fs, D]
+    b1o = None if b1 is None else b1.to(torch.bfloat16).contiguous()
+    hpre, hact = ops.dense_gemm_mxfp8(xq, xsc, w1q, w1s, bias=b1o, epilogue=L.EPI_BIAS_ACT, act=act, want_c2=True,
+                                      want_c=act != L.ACT_RELU)
+    hq, hs = ops.quantize_mxfp8(hact)
+    (w2q_b, w2s_b), (w2q, w2s) = _quantize_weight_both(w2, cache)      # backward pair [Fs, Dout]; forward pair [Dout, Fs]
+    y = ops.dense_gemm_mxfp8(hq, hs, w2q, w2s)
+    return y, (x2, hpre, hact, w1, w2, w1q_b, w1s_b, w2q_b, w2s_b), (act, None if b1 is None else b1.dtype)
+
+
+def dense_ffn_fp8_backward(saved, cfg, dy, needs, f8w: bool = False):
+    """The body of DenseFFNFP8.backward: (dx, gw1, gb1, gw2); `needs` = which of (x2, w1, b1, w2) take a gradient."""
+    x2, hpre, hact, w1, w2, w1q, w1s, w2q, w2s = saved
+    act, b1_dtype = cfg
+    dy = dy.contiguous()
+    T = dy.shape[0]
+    if f8w and needs[3]:
+        off = ops.dense_offsets(T, dy.device)
+        (dyt, dyts, poff), (dyq, dys) = ops.quantize_mxfp8_tokens(dy, off, 1, rows=True)
+    else:
+        dyq, dys = ops.quantize_mxfp8(dy)
+    dh = ops.dense_gemm_mxfp8(dyq, dys, w2q, w2s, epilogue=L.EPI_ACTGRAD, act=act, aux=hpre if hpre is not None else hact)
+    gw1 = gb1 = gw2 = dx = None
+    if needs[3]:
+        if f8w:
+            ht, hts, _ = ops.quantize_mxfp8_tokens(hact, off, 1)
+            gw2 = _dense_wgrad_fp8(ht, hts, dyt, dyts, poff, T, w2.dtype)     # [Fs, Dout]
+            del ht, hts, dyt, dyts
+        else:
+            gw2 = _dense_wgrad(hact, dy, w2.dtype)                     # [Fs, Dout]
+    dhq = dhs = None
+    if needs[1]:
+        if f8w:
+            off = ops.dense_offsets(T, dy.device)
+            xt, xts, poff = ops.quantize_mxfp8_tokens(x2, off, 1)
+            if needs[0]:
+                (dht, dhts, _), (dhq, dhs) = ops.quantize_mxfp8_tokens(dh, off, 1, rows=True)
+            else:
+                dht, dhts, _ = ops.quantize_mxfp8_tokens(dh, off, 1)
+            gw1 = _dense_wgrad_fp8(xt, xts, dht, dhts, poff, T, w1.dtype)    # [D, Fs]
+            del xt, xts, dht, dhts
+        else:
+            gw1 = _dense_wgrad(x2, dh, w1.dtype)                       # [D, Fs]
+    if b1_dtype is not None and needs[2]:
+        gb1 = _chunked_dense_colsum(dh, b1_dtype)
+    if needs[0]:
+        if dhq is None:
+            dhq, dhs = ops.quantize_mxfp8(dh)
+        dx = ops.dense_gemm_mxfp8(dhq, dhs, w1q, w1s)
+    return dx, gw1, gb1, gw2

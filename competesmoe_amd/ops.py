@@ -801,6 +801,46 @@ def quantize_mxfp8(x: torch.Tensor, transpose: bool = False):
     return q, s
 
 
+# A/B switch, read once per process: 0 = a gather followed by quantize_mxfp8 (two launches, the gathered rows read back) wherever the
+# one-pass kernels below would run; same bytes either way (tests/test_dispatch_quant_gpu.py)
+_DISPATCH_QUANT = os.environ.get("CSMOE_DISPATCH_QUANT", "1") != "0"
+
+
+def _dispatch_mxfp8(entry, tag: str, x2: torch.Tensor, index: torch.Tensor, bins: Bins, n_src: int, want_rows: bool):
+    _rows(tag, x2)
+    _need_cuda(x2)
+    D = x2.shape[1]
+    dev = x2.device
+    xs = torch.empty(bins.n, D, dtype=x2.dtype, device=dev) if want_rows else None
+    q = torch.empty(bins.n, D, dtype=torch.uint8, device=dev)
+    s = torch.empty(bins.n, D // 32, dtype=torch.uint8, device=dev)
+    # read the source rows, write K bf16 copies (when kept) and K quantised rows with their scales
+    nbytes = n_src * D * 2 + bins.n * (D * (3 if want_rows else 1) + D // 32)
+    with _timed(tag, nbytes):
+        L.check(entry(x2.data_ptr(), index.data_ptr(), bins.K, _ptr(xs), q.data_ptr(), s.data_ptr(), n_src, D, _dt(x2), _stream()), tag)
+    return xs, q, s
+
+
+def dispatch_rows_mxfp8(x2: torch.Tensor, bins: Bins, want_rows: bool = True):
+    """dispatch_rows + quantize_mxfp8 of the gathered rows in one pass (csmoe_dispatch_rows_mxfp8): (xs or None, q, s), the same
+    bytes.  bf16 rows, D % 32 == 0."""
+    if not _DISPATCH_QUANT:
+        xs = dispatch_rows(x2, bins)
+        return (xs if want_rows else None,) + quantize_mxfp8(xs)
+    return _dispatch_mxfp8(lib.csmoe_dispatch_rows_mxfp8, "dispatch_rows_mxfp8", x2, bins.perm, bins, bins.n, want_rows)
+
+
+def dispatch_tokens_mxfp8(x2: torch.Tensor, bins: Bins, want_rows: bool = True):
+    """dispatch_tokens + quantize_mxfp8 in one pass (csmoe_dispatch_tokens_mxfp8): every token row is read and quantised once and
+    stored to its K binned rows."""
+    if not _DISPATCH_QUANT:
+        xs = dispatch_tokens(x2, bins)
+        return (xs if want_rows else None,) + quantize_mxfp8(xs)
+    if x2.shape[0] * bins.K != bins.n:
+        raise ValueError(f"dispatch_tokens_mxfp8: {x2.shape[0]} rows do not match a binning of {bins.n} slots with K = {bins.K}")
+    return _dispatch_mxfp8(lib.csmoe_dispatch_tokens_mxfp8, "dispatch_tokens_mxfp8", x2, bins.slot_of, bins, x2.shape[0], want_rows)
+
+
 def quantize_mxfp8_both(x: torch.Tensor):
     """x [R, C] or [E, R, C] -> ((q, s), (qt, st)): both orientations of quantize_mxfp8 in one pass over x (weights: the forward
     and the backward product reduce over different dims).  Falls back to two passes when R or C is not a multiple of 32."""

@@ -10,7 +10,8 @@ from .smoe_perturbed import MoEPerturbedCosingGating, Selection
 from .block import MoEBlock
 from .smoe_ep import EPSMoeLayer
 from .competesmoe_ep import EPCompeteSMoE
+from .deepseek_ep import EPDeepSeekV2, EPDeepSeekV3
 
 __all__ = ["register_moe", "get_moe", "MOE_REGISTRY", "LoggingLayer", "RegularizedLayer", "OncePerIterLayer", "CVMMSel", "cvmm",
            "cvmm_prepare_sel2", "MoE", "SMoeLayer", "CompeteSMoE", "DeepSeekV2", "DeepSeekV3", "MoEPerturbedCosingGating", "Selection", "MoEBlock", "EPSMoeLayer",
-           "EPCompeteSMoE"]
+           "EPCompeteSMoE", "EPDeepSeekV2", "EPDeepSeekV3"]

@@ -30,27 +30,7 @@ from ..functional import RouterSelect
 from .competesmoe import CompeteSMoE
 from .moe import op_dtype
 from .register import register_moe
-from .smoe_ep import EPPackedExperts
-
-
-def _first_rank(group) -> int:
-    return dist.get_global_rank(group if group is not None else dist.group.WORLD, 0)
-
-
-def _broadcast(t: torch.Tensor, group) -> None:
-    """In-place broadcast of `t` from the group's first rank (through the current device when RCCL carries a host tensor)."""
-    if dist.get_world_size(group) == 1:
-        return
-    if dist.get_backend(group) == "nccl" and not t.is_cuda:
-        tmp = t.cuda()
-        dist.broadcast(tmp, src=_first_rank(group), group=group)
-        t.copy_(tmp.cpu())
-    elif dist.get_backend(group) != "nccl" and t.is_cuda:
-        tmp = t.cpu()
-        dist.broadcast(tmp, src=_first_rank(group), group=group)
-        t.copy_(tmp)
-    else:
-        dist.broadcast(t, src=_first_rank(group), group=group)
+from .smoe_ep import EPPackedExperts, _broadcast
 
 
 @register_moe("competesmoe_ep")

@@ -18,12 +18,33 @@ from .register import register_moe
 from .smoe import SMoeLayer
 
 
+def _first_rank(group) -> int:
+    return dist.get_global_rank(group if group is not None else dist.group.WORLD, 0)
+
+
+def _broadcast(t: torch.Tensor, group) -> None:
+    """In-place broadcast of `t` from the group's first rank (through the current device when RCCL carries a host tensor)."""
+    if dist.get_world_size(group) == 1:
+        return
+    if dist.get_backend(group) == "nccl" and not t.is_cuda:
+        tmp = t.cuda()
+        dist.broadcast(tmp, src=_first_rank(group), group=group)
+        t.copy_(tmp.cpu())
+    elif dist.get_backend(group) != "nccl" and t.is_cuda:
+        tmp = t.cpu()
+        dist.broadcast(tmp, src=_first_rank(group), group=group)
+        t.copy_(tmp)
+    else:
+        dist.broadcast(t, src=_first_rank(group), group=group)
+
+
 class EPPackedExperts:
-    """What the pretrain stack's expert-parallel layers share (smoe_ep, competesmoe_ep): the constructor contract -- `group`,
-    `chunks`, `direct`, this rank's slice of `keys` / `values` / `bias`, a RuntimeError without a process group, `is_att` and
-    `fp8_experts` refused, the replicated gate's (and `o_bias`'s) gradient summed over the group -- and the sparse step over the
-    exchange (EPFFNPacked / EPFFNPackedSlots).  Mixed in before the single-GPU layer class."""
+    """What the pretrain stack's expert-parallel layers share (smoe_ep, competesmoe_ep, deepseekv2/3_ep): the constructor contract --
+    `group`, `chunks`, `direct`, this rank's slice of `keys` / `values` / `bias`, a RuntimeError without a process group, `is_att` and
+    (unless the class sets `_fp8_experts_ok`) `fp8_experts` refused, the replicated gate's (and `o_bias`'s) gradient summed over the
+    group -- and the sparse step over the exchange (EPFFNPacked / EPFFNPackedSlots).  Mixed in before the single-GPU layer class."""
     _ep_name = "smoe_ep"
+    _fp8_experts_ok = False      # True on the layers whose sparse step has an fp8 form over the exchange (deepseek_ep.py)
 
     def __init__(self, *args, group=None, chunks: Optional[int] = None, direct: Optional[bool] = None, **kwargs):
         if not dist.is_initialized():
@@ -32,7 +53,7 @@ class EPPackedExperts:
         super().__init__(*args, **kwargs)
         if self.is_att:
             raise ValueError(f"{self._ep_name}: the MoE-attention projections are not expert-parallel")
-        if self.fp8_experts:
+        if self.fp8_experts and not self._fp8_experts_ok:
             raise ValueError(f"{self._ep_name}: args.fp8_experts is a single-GPU path")
         self.chunks = chunks        # groups of local experts whose exchanges overlap the GEMMs; None: CSMOE_EP_CHUNKS, else 2 (1 at P=1)
         self.direct = direct        # one message per (peer, local expert), no regroup passes; None: CSMOE_EP_DIRECT, else off

@@ -365,6 +365,15 @@ int csmoe_grouped_gemm_f32w(const void* A, int64_t lda, const void* const* b_ptr
  * transposed product (dX = dY . W for a weight stored [N, K]). */
 int csmoe_quantize_mxfp8(const void* x, const void* const* x_ptrs, int E, int64_t ldx, int R, int C, int dtype, int transpose,
                          void* q, void* s, csmoe_stream_t stream);
+/* Gather and quantise in one pass: xs as csmoe_dispatch_rows / csmoe_dispatch_tokens write it (xs may be null: no bf16 copy), and
+ * q [n, D] / s [n, D/32] byte for byte what csmoe_quantize_mxfp8 (transpose == 0) writes for xs.  Replaces the gather of
+ * cvmm.py:114-119 followed by this library's own quantiser (the reference has no fp8): the gathered bf16 rows are not read back.
+ * The tokens form has n = T * K destination rows.  CSMOE_BF16 only, D % 32 == 0, x / xs 16-byte aligned (else CSMOE_ERR_INVALID
+ * before anything is launched); n == 0 / T == 0 is a no-op. */
+int csmoe_dispatch_rows_mxfp8(const void* x, const int32_t* perm, int K, void* xs, uint8_t* q, uint8_t* s, int n, int D, int dtype,
+                              csmoe_stream_t stream);
+int csmoe_dispatch_tokens_mxfp8(const void* x, const int32_t* slot_of, int K, void* xs, uint8_t* q, uint8_t* s, int T, int D,
+                                int dtype, csmoe_stream_t stream);
 /* Both orientations in one pass over the source (weights are needed along one dim by the forward product and along the other by
  * the backward product): q [E, R, C] / s [E, R, C/32] and qt [E, C, R] / st [E, C, R/32], bit-identical to the two separate calls.
  * R % 32 == 0, C % 32 == 0, 16-byte aligned rows. */
