@@ -19,7 +19,8 @@ LIB_PATH = os.environ.get("CSMOE_LIB") or os.path.join(_HERE, "lib", "libcsmoe_h
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_GELU_TANH, ACT_SILU, ACT_QUICK_GELU = 0, 1, 2, 3, 4, 5
-SEL_SOFTMAX, SEL_RAW, SEL_TOPK_SOFTMAX, SEL_SIGMOID, SEL_TOPK_SIGMOID = 0, 1, 2, 3, 4
+SEL_SOFTMAX, SEL_RAW, SEL_TOPK_SOFTMAX, SEL_SIGMOID, SEL_TOPK_SIGMOID, SEL_TEMP_SOFTMAX_TOPK = 0, 1, 2, 3, 4, 5
+TEMP_P_BF16, TEMP_W_BF16, COS_OPER_BF16 = 1, 2, 4      # rounding points of the cosine router (include/csmoe.h)
 COMBINE_SEQ, COMBINE_DOT, COMBINE_SEQ_RW = 0, 1, 2
 B_NK, B_KN = 0, 1
 EPI_PLAIN, EPI_BIAS, EPI_BIAS_ACT, EPI_ACTGRAD, EPI_ROUND_BIAS32_ACT, EPI_SOFTPLUS_ROWSUM, EPI_SOFTPLUS_GRAD = 0, 1, 2, 3, 4, 5, 6
@@ -47,6 +48,11 @@ SIGNATURES = {
     "csmoe_gate_select_ok": (_i, [_i, _i, _i, _i, _i]),
     "csmoe_gate_select_rows": (_i, []),
     "csmoe_gate_select": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, C.c_float, _i, _p, _p, _p, _p, _p, _p]),
+    "csmoe_cosine_select_ok": (_i, [_i, _i, _i, _i, _i]),
+    "csmoe_cosine_select_work_ints": (_l, [_i]),
+    "csmoe_cosine_select": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "csmoe_cosine_select_bwd_parts": (_i, [_i]),
+    "csmoe_cosine_select_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, C.c_float, C.c_float, _i, _p, _p, _p, _p]),
     "csmoe_dispatch_rows": (_i, [_p, _p, _i, _p, _i, _i, _i, _p]),
     "csmoe_dispatch_tokens": (_i, [_p, _p, _i, _p, _i, _i, _i, _p]),
     "csmoe_dispatch_vec_ok": (_i, [_p, _p, _i, _i]),

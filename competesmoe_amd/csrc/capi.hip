@@ -62,6 +62,14 @@ int k_bin_tokens_hist(const int32_t*, int, int, int, const int32_t*, int32_t*, i
 bool k_gate_select_ok(int T, int D, int E, int K, int dtype, const void* x, const void* wg);
 int k_gate_select_rows();
 int k_gate_select(const void*, const void*, int, int, int, int, int, int, float, void*, float*, int32_t*, float*, int32_t*, hipStream_t);
+bool k_cosine_select_ok(int T, int D, int E, int K, int dtype, const void* x, const void* wr);
+int64_t k_cosine_select_work_ints(int T);
+int k_cosine_select(const void* x, const void* wr, const float* emb, int T, int D, int E, int K, int flags, float temperature, float eps,
+                    void* reduced, void* logits, float* p, int32_t* idx, float* w, int32_t* block_hist, int32_t* work, hipStream_t st);
+int k_cosine_select_bwd_parts(int T);
+int k_cosine_select_bwd(const void* reduced, const float* emb, const void* logits, const int32_t* idx, const float* w, const float* dw,
+                        const float* dp, const void* dlogits, int T, int E, int K, int flags, float temperature, float eps,
+                        void* d_reduced, float* d_emb, float* part, hipStream_t st);
 int k_dispatch_rows(const void*, const int32_t*, int, void*, int, int, int, hipStream_t);
 int k_dispatch_tokens(const void*, const int32_t*, int, void*, int, int, int, hipStream_t);
 int k_dispatch_quant_mxfp8(const void* x, const int32_t* index, int K, void* xs, void* q, void* s, int n, int D, int tokens,
@@ -197,8 +205,9 @@ int csmoe_router_select(const void* scores, int dtype, int T, int E, int K, int 
   CSMOE_CHECK_ARG(dtype_ok(dtype), "router_select: bad dtype %d", dtype);
   CSMOE_CHECK_ARG(T >= 0 && E > 0 && E <= 1024, "router_select: E=%d out of range (1..1024)", E);
   CSMOE_CHECK_ARG(K > 0 && K <= E && K <= 64, "router_select: K=%d out of range (1..min(E,64))", K);
-  CSMOE_CHECK_ARG(sel_mode >= 0 && sel_mode <= 4, "router_select: bad mode %d", sel_mode);
+  CSMOE_CHECK_ARG(sel_mode >= 0 && sel_mode <= 5, "router_select: bad mode %d", sel_mode);
   CSMOE_CHECK_ARG(sel_mode != CSMOE_SEL_TOPK_SIGMOID || sel_param != 0.f, "router_select: SEL_TOPK_SIGMOID needs a non-zero scale");
+  CSMOE_CHECK_ARG(sel_mode != CSMOE_SEL_TEMP_SOFTMAX_TOPK || sel_param > 0.f, "router_select: SEL_TEMP_SOFTMAX_TOPK needs a positive temperature");
   if (T == 0) return CSMOE_OK;
   CSMOE_CHECK_ARG(scores && idx && w, "router_select: null pointer");
   return k_router_select(scores, dtype, T, E, K, sel_mode, round_sum_bf16, sel_param, softmax, idx, w, (hipStream_t)stream);
@@ -209,8 +218,9 @@ int csmoe_router_select_bwd(const void* scores, int dtype, int T, int E, int K, 
                             void* dscores, csmoe_stream_t stream) {
   CSMOE_CHECK_ARG(dtype_ok(dtype), "router_select_bwd: bad dtype %d", dtype);
   CSMOE_CHECK_ARG(T >= 0 && E > 0 && E <= 1024 && K > 0 && K <= E && K <= 64, "router_select_bwd: bad shape");
-  CSMOE_CHECK_ARG(sel_mode >= 0 && sel_mode <= 4, "router_select_bwd: bad mode %d", sel_mode);
+  CSMOE_CHECK_ARG(sel_mode >= 0 && sel_mode <= 5, "router_select_bwd: bad mode %d", sel_mode);
   CSMOE_CHECK_ARG(sel_mode != CSMOE_SEL_TOPK_SIGMOID || sel_param != 0.f, "router_select_bwd: SEL_TOPK_SIGMOID needs a non-zero scale");
+  CSMOE_CHECK_ARG(sel_mode != CSMOE_SEL_TEMP_SOFTMAX_TOPK || sel_param > 0.f, "router_select_bwd: SEL_TEMP_SOFTMAX_TOPK needs a positive temperature");
   if (T == 0) return CSMOE_OK;
   CSMOE_CHECK_ARG(scores && idx && w && dscores, "router_select_bwd: null pointer");
   CSMOE_CHECK_ARG(softmax || (sel_mode != CSMOE_SEL_SOFTMAX && !dsoftmax), "router_select_bwd: softmax required");
@@ -239,6 +249,38 @@ int csmoe_affinity_finish(const float* partial, int M, int ntiles, int D, void* 
   CSMOE_CHECK_ARG(M >= 0 && ntiles > 0 && D > 0 && aff_stride > 0 && dtype_ok(aff_dtype), "affinity_finish: bad arguments");
   CSMOE_CHECK_ARG(M == 0 || (partial && aff), "affinity_finish: null pointer");
   return k_affinity_finish(partial, M, ntiles, D, aff, aff_stride, aff_dtype, (hipStream_t)stream);
+}
+
+int csmoe_cosine_select_ok(int T, int D, int E, int K, int dtype) {
+  return T >= 0 && D > 0 && K > 0 && k_cosine_select_ok(T, D, E, K, dtype, nullptr, nullptr) ? 1 : 0;
+}
+
+int64_t csmoe_cosine_select_work_ints(int T) { return k_cosine_select_work_ints(T < 0 ? 0 : T); }
+
+int csmoe_cosine_select(const void* x, const void* w_red, const float* emb, int T, int D, int E, int K, int flags, float temperature,
+                        float eps, int dtype, void* reduced, void* logits, float* p, int32_t* idx, float* w, int32_t* block_hist,
+                        int32_t* work, csmoe_stream_t stream) {
+  CSMOE_CHECK_ARG(T >= 0 && D > 0 && E > 0 && K > 0 && K <= E, "cosine_select: bad shape T=%d D=%d E=%d K=%d", T, D, E, K);
+  CSMOE_CHECK_ARG(flags >= 0 && flags <= 7 && temperature > 0.f && eps > 0.f, "cosine_select: bad flags %d / temperature / eps", flags);
+  CSMOE_CHECK_ARG(k_cosine_select_ok(T, D, E, K, dtype, x, w_red),
+                  "cosine_select: needs bf16, E even and <= 64, D a multiple of 8, 16-byte aligned operands (csmoe_cosine_select_ok)");
+  CSMOE_CHECK_ARG(work, "cosine_select: null work buffer");
+  CSMOE_CHECK_ARG(T == 0 || (x && w_red && emb && reduced && logits && p && idx && w), "cosine_select: null pointer");
+  return k_cosine_select(x, w_red, emb, T, D, E, K, flags, temperature, eps, reduced, logits, p, idx, w, block_hist, work,
+                         (hipStream_t)stream);
+}
+
+int csmoe_cosine_select_bwd_parts(int T) { return k_cosine_select_bwd_parts(T < 0 ? 0 : T); }
+
+int csmoe_cosine_select_bwd(const void* reduced, const float* emb, const void* logits, const int32_t* idx, const float* w,
+                            const float* dw, const float* dp, const void* dlogits, int T, int E, int K, int flags, float temperature,
+                            float eps, int dtype, void* d_reduced, float* d_emb, float* part, csmoe_stream_t stream) {
+  CSMOE_CHECK_ARG(dtype == CSMOE_BF16, "cosine_select_bwd: bf16 only (dtype %d)", dtype);
+  CSMOE_CHECK_ARG(T >= 0 && E >= 2 && E <= 64 && E % 2 == 0 && K > 0 && K <= E, "cosine_select_bwd: bad shape T=%d E=%d K=%d", T, E, K);
+  CSMOE_CHECK_ARG(flags >= 0 && flags <= 7 && temperature > 0.f && eps > 0.f, "cosine_select_bwd: bad flags %d / temperature / eps", flags);
+  CSMOE_CHECK_ARG(emb && d_emb && part && (T == 0 || (reduced && logits && idx && w && d_reduced)), "cosine_select_bwd: null pointer");
+  return k_cosine_select_bwd(reduced, emb, logits, idx, w, dw, dp, dlogits, T, E, K, flags, temperature, eps, d_reduced, d_emb, part,
+                             (hipStream_t)stream);
 }
 
 int csmoe_gate_select_ok(int T, int D, int E, int K, int dtype) {

@@ -28,6 +28,11 @@ __global__ void __launch_bounds__(256) router_select_kernel(const void* scores, 
     int e = lane + 64 * v;
     s[v] = e < E ? load_score(scores, base + e, dtype) : -INFINITY;
   }
+  if (mode == CSMOE_SEL_TEMP_SOFTMAX_TOPK) {
+    select_row_temp<VPL>(s, lane, E, K, round_sum_bf16, sel_param, dtype, softmax ? softmax + base : nullptr, idx + (int64_t)t * K,
+                         w + (int64_t)t * K);
+    return;
+  }
   select_row<VPL>(s, lane, E, K, mode, round_sum_bf16, sel_param, dtype, softmax ? softmax + base : nullptr, idx + (int64_t)t * K,
                   w + (int64_t)t * K);
 }
@@ -42,6 +47,57 @@ __global__ void __launch_bounds__(256) router_select_bwd_kernel(const void* scor
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (t >= T) return;
   const int64_t base = (int64_t)t * E;
+  if (mode == CSMOE_SEL_TEMP_SOFTMAX_TOPK) {
+    // autograd of xmoe.py:90-91 + `_keepTopk`: softmax over the K keys (a bf16 tensor op under CSMOE_TEMP_W_BF16: its gradient is
+    // rounded), scattered into d p and added to the losses' d p (in bf16 when p is a bf16 tensor), the fp32 softmax's backward with
+    // ITS OWN output -- the unrounded p, recomputed from the scores -- rounded to the scores' dtype (the input's cast), then the
+    // division by the temperature in that dtype.
+    const bool pb = round_sum_bf16 & CSMOE_TEMP_P_BF16, wb = round_sum_bf16 & CSMOE_TEMP_W_BF16;
+    int myi = -1;
+    float mydw = 0.f, myw = 0.f;
+    if (lane < K) {
+      myi = idx[(int64_t)t * K + lane];
+      mydw = dw ? dw[(int64_t)t * K + lane] : 0.f;
+      myw = w[(int64_t)t * K + lane];
+    }
+    const float dot = wave_sum(mydw * myw);
+    float dv = myw * (mydw - dot);
+    if (wb) dv = (float)(bf16)dv;
+    float z[VPL], ex[VPL], g[VPL], mx = -INFINITY, sum = 0.f;
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+      const int e = lane + 64 * v;
+      z[v] = e < E ? round_dt(load_score(scores, base + e, dtype) / sel_param, dtype) : -INFINITY;
+      mx = fmaxf(mx, z[v]);
+    }
+    mx = wave_max(mx);
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+      const int e = lane + 64 * v;
+      ex[v] = e < E ? expf(z[v] - mx) : 0.f;
+      sum += ex[v];
+      g[v] = (dsoftmax && e < E) ? dsoftmax[base + e] : 0.f;
+    }
+    sum = wave_sum(sum);
+    for (int k = 0; k < K; ++k) {
+      const int ei = __shfl(myi, k, 64);
+      const float d = __shfl(dv, k, 64);
+#pragma unroll
+      for (int v = 0; v < VPL; ++v)
+        if (lane + 64 * v == ei) g[v] = pb ? (float)(bf16)(g[v] + d) : g[v] + d;
+    }
+    float inner = 0.f;
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) inner += g[v] * (ex[v] / sum);
+    inner = wave_sum(inner);
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+      const int e = lane + 64 * v;
+      const float dz = round_dt((ex[v] / sum) * (g[v] - inner), dtype);
+      if (e < E) store_score(dscores, base + e, dz / sel_param, dtype);
+    }
+    return;
+  }
   // lane k (< K) holds slot k
   int myi = -1;
   float mydw = 0.f, myw = 0.f, myv = 0.f;

@@ -1,5 +1,5 @@
 // Router selection of ONE token row by one wave (lane l holds scores l, l+64, ...: VPL values per lane, E <= 64*VPL): fp32 softmax,
-// K rounds of wave arg-max with the lowest-index tie break, and the renormalised weights of the five selection modes of
+// K rounds of wave arg-max with the lowest-index tie break, and the renormalised weights of the six selection modes of
 // include/csmoe.h.  Shared by router_select_kernel (moe_kernels.hip) and the one-pass router (router_fused.hip), so that the fused
 // path selects and weighs bit-identically.
 // (moe_model/model/moe/moe.py:113-132, smoe.py:44, competesmoe.py:246-255; moe_pretrain_model/layers/moe/deepseekv2.py:140-142,
@@ -98,6 +98,61 @@ __device__ __forceinline__ void select_row(const float (&s)[VPL], int lane, int 
     denom = vsum + 1e-20f;
     wk = myv / denom;
   }
+  if (lane < K) { w_row[lane] = wk; idx_row[lane] = myi; }
+}
+
+// CSMOE_SEL_TEMP_SOFTMAX_TOPK (the XMoE cosine router, moe_model/model/moe/xmoe.py:90-91 + 48-51): p = fp32 softmax of
+// (score / temperature, the quotient rounded to the scores' dtype), cast to bf16 under CSMOE_TEMP_P_BF16; top-K of p; w = softmax over
+// the K values, rounded to bf16 under CSMOE_TEMP_W_BF16; sm_row receives p.  A routine of its own -- same reduction trees, same
+// arg-max -- so that the code of the five older rules, and with it the one-pass router's specialised kernel, stays as it was.
+template <int VPL>
+__device__ __forceinline__ void select_row_temp(const float (&s)[VPL], int lane, int E, int K, int tflags, float temperature, int dtype,
+                                                float* sm_row, int32_t* idx_row, float* w_row) {
+  float key[VPL], z[VPL];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int v = 0; v < VPL; ++v) {
+    z[v] = round_dt(s[v] / temperature, dtype);
+    mx = fmaxf(mx, z[v]);
+  }
+  mx = wave_max(mx);
+  float ex[VPL], sum = 0.f;
+#pragma unroll
+  for (int v = 0; v < VPL; ++v) {
+    int e = lane + 64 * v;
+    ex[v] = e < E ? expf(z[v] - mx) : 0.f;
+    sum += ex[v];
+  }
+  sum = wave_sum(sum);
+#pragma unroll
+  for (int v = 0; v < VPL; ++v) {
+    int e = lane + 64 * v;
+    float p = ex[v] / sum;
+    if (tflags & CSMOE_TEMP_P_BF16) p = (float)(bf16)p;
+    if (sm_row && e < E) sm_row[e] = p;
+    key[v] = e < E ? p : -INFINITY;
+  }
+  float myv = 0.f;
+  int myi = 0;
+  for (int k = 0; k < K; ++k) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+      int e = lane + 64 * v;
+      if (key[v] > bv || (key[v] == bv && e < bi)) { bv = key[v]; bi = e; }
+    }
+    wave_argmax(bv, bi);
+#pragma unroll
+    for (int v = 0; v < VPL; ++v)
+      if (lane + 64 * v == bi) key[v] = -INFINITY;
+    if (lane == k) { myv = bv; myi = bi; }
+  }
+  float top = __shfl(myv, 0, 64);
+  float ek = lane < K ? expf(myv - top) : 0.f;
+  float es = wave_sum(ek);
+  float wk = ek / es;
+  if (tflags & CSMOE_TEMP_W_BF16) wk = (float)(bf16)wk;
   if (lane < K) { w_row[lane] = wk; idx_row[lane] = myi; }
 }
 
@@ -223,4 +278,53 @@ __device__ __forceinline__ void select_row_g16(const float (&s)[4], int l16, int
                                                float sel_param, int dtype, bool live, float* sm_row, int32_t* idx_row, float* w_row) {
   int myi[4];
   select_row_g16(s, l16, E, K, mode, round_sum_bf16, sel_param, dtype, live, sm_row, idx_row, w_row, myi);
+}
+
+// CSMOE_SEL_TEMP_SOFTMAX_TOPK with sixteen lanes per row: the bits of select_row_temp<1> (the trees of select_row_g16)
+__device__ __forceinline__ void select_row_temp_g16(const float (&s)[4], int l16, int E, int K, int tflags, float temperature, int dtype,
+                                                    bool live, float* sm_row, int32_t* idx_row, float* w_row, int (&myi)[4]) {
+  float key[4], ex[4], z[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) z[j] = round_dt(s[j] / temperature, dtype);
+  float mx = g16_max(fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3])));
+#pragma unroll
+  for (int j = 0; j < 4; ++j) ex[j] = (l16 + 16 * j) < E ? expf(z[j] - mx) : 0.f;
+  const float sum = g16_sum64(ex);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int e = l16 + 16 * j;
+    float p = ex[j] / sum;
+    if (tflags & CSMOE_TEMP_P_BF16) p = (float)(bf16)p;
+    if (live && sm_row && e < E) sm_row[e] = p;
+    key[j] = e < E ? p : -INFINITY;
+  }
+  float myv[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) myi[j] = 0;
+  for (int k = 0; k < K; ++k) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int e = l16 + 16 * j;
+      if (key[j] > bv || (key[j] == bv && e < bi)) { bv = key[j]; bi = e; }
+    }
+    g16_argmax(bv, bi);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (l16 + 16 * j == bi) key[j] = -INFINITY;
+      if (l16 + 16 * j == k) { myv[j] = bv; myi[j] = bi; }
+    }
+  }
+  const float top = __shfl(myv[0], 0, 16);
+  float ek[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) ek[j] = (l16 + 16 * j) < K ? expf(myv[j] - top) : 0.f;
+  const float es = g16_sum64(ek);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float wk = ek[j] / es;
+    if (tflags & CSMOE_TEMP_W_BF16) wk = (float)(bf16)wk;
+    if (live && l16 + 16 * j < K) { w_row[l16 + 16 * j] = wk; idx_row[l16 + 16 * j] = myi[j]; }
+  }
 }

@@ -276,6 +276,88 @@ class GateSelect(torch.autograd.Function):
         return dx, dwg, None, None, None, None
 
 
+class CosineSelect(torch.autograd.Function):
+    """XMoE's router in ONE launch that reads x once (csmoe_cosine_select): reduced = x @ expert_sel^T, cosine logits against the
+    renormalised expert embeddings, p = softmax(logits / temperature), top-K of p and the softmax over the K -- `inp_reduction` +
+    `_cosine` + `_make_finite` + F.softmax + `_keepTopk` (moe_model/model/moe/xmoe.py:80-91; moe_pretrain_model/layers/moe/xmoe.py:
+    143-162).  Returns (logits, p fp32 holding the values rounded as `flags` say, idx int32, w fp32).  `flags`: _lib.TEMP_P_BF16 |
+    TEMP_W_BF16 | COS_OPER_BF16, the reference's rounding points (include/csmoe.h).  `emb` is the parameter AFTER its in-place
+    renormalisation; its gradient is the gradient w.r.t. those values.  Backward: one row kernel through selection, softmax, cosine
+    product and normalisation (csmoe_cosine_select_bwd, deterministic d emb), then the two gate products of GateLogits.backward."""
+
+    @staticmethod
+    def forward(ctx, x2, expert_sel, emb, K: int, flags: int, temperature: float = 0.3, eps: float = 1e-4):
+        x2 = x2.contiguous()
+        wr = expert_sel.contiguous()
+        if wr.dtype != x2.dtype:
+            wr = wr.to(x2.dtype)
+        emb32 = emb.detach().to(torch.float32, copy=True).contiguous()      # a copy: the parameter is rescaled in place every forward
+        reduced, logits, p, idx, w, status = ops.cosine_select(x2, wr, emb32, K, flags, temperature, eps)
+        ctx.save_for_backward(x2, wr, emb32, reduced, logits, idx, w)
+        ctx.cfg = (K, flags, temperature, eps)
+        ctx.dtypes = (expert_sel.dtype, emb.dtype)
+        ctx.mark_non_differentiable(idx)
+        ctx.set_materialize_grads(False)
+        CosineSelect.last_status = status
+        return logits, p, idx, w
+
+    last_status = None      # [1] int32 on the device: non-finite rows of the latest call (diagnostics; reading it synchronises)
+
+    @staticmethod
+    def backward(ctx, dlogits, dp, _didx, dw):
+        x2, wr, emb32, reduced, logits, idx, w = ctx.saved_tensors
+        K, flags, temperature, eps = ctx.cfg
+        if dlogits is None and dp is None and dw is None:
+            return None, None, None, None, None, None, None
+        dlogits = None if dlogits is None else dlogits.contiguous().to(logits.dtype)
+        dp = None if dp is None else dp.contiguous().float()
+        dw = None if dw is None else dw.contiguous().float()
+        d_red, d_emb = ops.cosine_select_bwd(reduced, emb32, logits, idx, w, dw, dp, dlogits, K, flags, temperature, eps)
+        dx = dwr = demb = None
+        small = ops.gate_bwd_small_ok(x2.shape[1], wr.shape[0], x2.dtype)
+        if ctx.needs_input_grad[0]:
+            dx = ops.gate_bwd_dx(d_red, wr) if small else ops.dense_gemm(d_red, wr, L.B_KN)
+        if ctx.needs_input_grad[1]:
+            dwr = _gate_wgrad(d_red, x2, ctx.dtypes[0], small)
+        if ctx.needs_input_grad[2]:
+            if flags & L.COS_OPER_BF16:          # the bf16 matmul's backward hands its operand a bf16 gradient
+                d_emb = d_emb.to(torch.bfloat16)
+            demb = d_emb.to(ctx.dtypes[1])
+        return dx, dwr, demb, None, None, None, None
+
+
+def make_finite(scores: torch.Tensor) -> torch.Tensor:
+    """`_make_finite` (xmoe.py:72-77) without its host synchronisation: non-finite entries become the smallest finite one.  The
+    assigned entries carry no gradient (as in the one-pass kernel; upstream's index assignment would send theirs to the minimum)."""
+    ok = scores.isfinite()
+    low = torch.where(ok, scores, torch.full_like(scores, float("inf"))).min()
+    return torch.where(ok, scores, low.detach())
+
+
+def cosine_route_unfused(x2, expert_sel, sel_bias, emb, K: int, flags: int, temperature: float = 0.3, eps: float = 1e-4):
+    """The same router where the one-pass kernel does not take the shape (fp32, E > 64, a `sel_bias`, CSMOE_FUSED_ROUTER=0): the
+    reduction is the gate kernel (GateLogits), the [T, E/2]- and [T, E]-sized cosine math torch ops placed as `flags` say, the
+    selection the router kernel with CSMOE_SEL_TEMP_SOFTMAX_TOPK.  Returns (logits, p, idx, w) like CosineSelect.
+
+    Known deviation: `sel_bias` is added to the reduction AFTER the gate kernel has rounded it to the compute dtype, and the sum is
+    rounded again; F.linear(x, expert_sel, sel_bias) adds it to the fp32 accumulator and rounds once.  In fp32 (the only captured
+    `sel_bias` fixture) the two agree to the fixture's 1e-5; under bf16 autocast `reduced` can differ from the reference's by one
+    bf16 ulp per element, which no fixture covers."""
+    reduced = GateLogits.apply(x2, expert_sel)
+    with torch.autocast("cuda", enabled=False):
+        if sel_bias is not None:
+            reduced = reduced + sel_bias.to(reduced.dtype)
+        m = torch.nn.functional.normalize(reduced.float(), p=2.0, dim=-1, eps=eps)
+        embf = emb.float()
+        if flags & L.COS_OPER_BF16:
+            cos = torch.matmul(m.to(torch.bfloat16), embf.to(torch.bfloat16).transpose(0, 1))
+        else:
+            cos = torch.matmul(m, embf.transpose(0, 1))
+        logits = make_finite(cos.to(reduced.dtype))
+    p, idx, w = RouterSelect.apply(logits, K, L.SEL_TEMP_SOFTMAX_TOPK, flags & 3, temperature)
+    return logits, p, idx, w
+
+
 class RouterAux(torch.autograd.Function):
     """(balance loss fp32, z-loss in logits.dtype) of the LLaVA stack in two launches, one for the backward --
     `balanceloss` (moe_model/model/moe/moe.py:90-110: mean_n softmax x mean_n one_hot(top-1), mean over (b, e), x E^2) and

@@ -161,6 +161,62 @@ def gate_select(x2: torch.Tensor, w_gate: torch.Tensor, K: int, mode: int, round
     return logits, sm, idx, w
 
 
+def cosine_select_ok(x2: torch.Tensor, w_red: torch.Tensor, E: int, K: int) -> bool:
+    """Does the one-pass cosine router (csmoe_cosine_select) take this shape?  bf16, E even and <= 64, D % 8 == 0, dense 16-byte
+    aligned operands.  CSMOE_FUSED_ROUTER=0 turns it off, as it does the one-pass linear router (A/B runs)."""
+    if os.environ.get("CSMOE_FUSED_ROUTER", "1") == "0" or not x2.is_cuda:
+        return False
+    T, D = x2.shape
+    # an fp32 master of the reduction matrix is cast to the operand dtype first (a fresh, aligned tensor)
+    w_ok = w_red.dtype != x2.dtype or (w_red.data_ptr() % 16 == 0 and w_red.is_contiguous())
+    return (2 * w_red.shape[0] == E and w_red.shape[1] == D and bool(lib.csmoe_cosine_select_ok(T, D, E, K, _dt(x2)))
+            and x2.data_ptr() % 16 == 0 and x2.is_contiguous() and w_ok)
+
+
+def cosine_select(x2: torch.Tensor, w_red: torch.Tensor, emb: torch.Tensor, K: int, flags: int, temperature: float = 0.3,
+                  eps: float = 1e-4, want_hist: bool = True):
+    """XMoE's router in one launch that reads x2 once (+ the one-workgroup patch launch): (reduced [T,R], logits [T,E], p [T,E] fp32,
+    idx [T,K] int32, w [T,K] fp32, status [1] int32 = number of non-finite rows of this call).  `emb`: fp32 [E,R], renormalised."""
+    _need_cuda(x2, w_red, emb)
+    _rows("cosine_select", x2, w_red, emb)
+    if emb.dtype != torch.float32:
+        raise ValueError("csmoe cosine_select: emb must be the fp32 copy of the expert embeddings")
+    T, D = x2.shape
+    E, R = emb.shape
+    dev = x2.device
+    reduced = torch.empty(T, R, dtype=x2.dtype, device=dev)
+    logits = torch.empty(T, E, dtype=x2.dtype, device=dev)
+    p = torch.empty(T, E, dtype=torch.float32, device=dev)
+    idx = torch.empty(T, K, dtype=torch.int32, device=dev)
+    w = torch.empty(T, K, dtype=torch.float32, device=dev)
+    rows = int(lib.csmoe_gate_select_rows())
+    hist = torch.empty((T + rows - 1) // rows, E, dtype=torch.int32, device=dev) if want_hist and T > 0 else None
+    work = torch.empty(int(lib.csmoe_cosine_select_work_ints(T)), dtype=torch.int32, device=dev)
+    with _timed("cosine_select", T * D * x2.element_size()):
+        L.check(lib.csmoe_cosine_select(x2.data_ptr(), w_red.data_ptr(), emb.data_ptr(), T, D, E, K, int(flags), float(temperature),
+                                        float(eps), _dt(x2), reduced.data_ptr(), logits.data_ptr(), p.data_ptr(), idx.data_ptr(),
+                                        w.data_ptr(), _ptr(hist), work.data_ptr(), _stream()), "cosine_select")
+    global _ROUTE_HIST
+    _ROUTE_HIST = (idx, idx._version, hist, rows * K) if hist is not None else None
+    return reduced, logits, p, idx, w, work[:1]
+
+
+def cosine_select_bwd(reduced, emb, logits, idx, w, dw, dp, dlogits, K: int, flags: int, temperature: float = 0.3, eps: float = 1e-4):
+    """(d_reduced [T,R] in reduced.dtype, d_emb [E,R] fp32) of csmoe_cosine_select_bwd; dw / dp fp32 or None, dlogits in
+    logits.dtype or None.  Deterministic (fixed-order partial tables)."""
+    _rows("cosine_select_bwd", reduced, emb, logits, idx, w, dw, dp, dlogits)
+    T, R = reduced.shape
+    E = emb.shape[0]
+    dev = reduced.device
+    d_reduced = torch.empty_like(reduced)
+    d_emb = torch.empty(E, R, dtype=torch.float32, device=dev)
+    part = torch.empty(int(lib.csmoe_cosine_select_bwd_parts(T)) * E * R, dtype=torch.float32, device=dev)
+    L.check(lib.csmoe_cosine_select_bwd(reduced.data_ptr(), emb.data_ptr(), logits.data_ptr(), idx.data_ptr(), w.data_ptr(), _ptr(dw),
+                                        _ptr(dp), _ptr(dlogits), T, E, K, int(flags), float(temperature), float(eps), _dt(reduced),
+                                        d_reduced.data_ptr(), d_emb.data_ptr(), part.data_ptr(), _stream()), "cosine_select_bwd")
+    return d_reduced, d_emb
+
+
 def router_select(scores: torch.Tensor, K: int, mode: int, round_sum_bf16: bool, want_softmax: bool = True, param: float = 1.0):
     _need_cuda(scores)
     _rows("router_select", scores)

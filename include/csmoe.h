@@ -37,8 +37,17 @@ enum {
   CSMOE_SEL_TOPK_SOFTMAX = 2, /* topk(logits) -> softmax over the K  moe_pretrain_model/layers/moe/deepseekv2.py:140-142 */
   CSMOE_SEL_SIGMOID = 3,  /* topk(sigmoid in the scores' dtype) -> w/(fp32 sum+1e-20), fp32 quotient (under CUDA autocast `sum` is an
                              fp32-policy op)                          moe_pretrain_model/layers/moe/deepseekv3.py:147-151 */
-  CSMOE_SEL_TOPK_SIGMOID = 4 /* topk(logits) -> sigmoid(v / sel_param) -> w/sum   (`norm_sigmoid` + `scale_weight`,
+  CSMOE_SEL_TOPK_SIGMOID = 4, /* topk(logits) -> sigmoid(v / sel_param) -> w/sum   (`norm_sigmoid` + `scale_weight`,
                                 moe_pretrain_model/layers/moe/competesmoe.py:476-483)                                    */
+  CSMOE_SEL_TEMP_SOFTMAX_TOPK = 5 /* p = softmax(fp32) of (score / sel_param rounded to the scores' dtype) -> topk(p) -> softmax over
+                                the K values; the `softmax` output holds p.  `round_sum_bf16` is a set of CSMOE_TEMP_* flags here
+                                (XMoE: moe_model/model/moe/xmoe.py:90-91, 48-51; moe_pretrain_model/layers/moe/xmoe.py:161-162) */
+};
+/* Rounding points of the cosine router (flags; the first two are SEL_TEMP_SOFTMAX_TOPK's `round_sum_bf16`). */
+enum {
+  CSMOE_TEMP_P_BF16 = 1,    /* p is cast to bf16 before the top-K (`.to(x.dtype)` of a bf16 module)                          */
+  CSMOE_TEMP_W_BF16 = 2,    /* the softmax over the K keys is a bf16 tensor op                                                */
+  CSMOE_COS_OPER_BF16 = 4   /* the cosine product's operands are rounded to bf16 (`matmul` under bf16 autocast)              */
 };
 
 /* Combine rounding rule. */
@@ -153,6 +162,38 @@ int csmoe_gate_select_rows(void);
 int csmoe_gate_select(const void* x, const void* w_gate, int T, int D, int E, int K, int sel_mode, int round_sum_bf16,
                       float sel_param, int dtype, void* logits, float* softmax, int32_t* idx, float* w, int32_t* block_hist,
                       csmoe_stream_t stream);
+
+/* ---- one-pass cosine router (XMoE) ----------------------------------------------------------------------
+ * `inp_reduction(x)` + `_cosine` + `_make_finite` + softmax(logits / temperature) + `_keepTopk` (+ the counting pass of
+ * csmoe_bin_tokens) of moe_model/model/moe/xmoe.py:80-91 / moe_pretrain_model/layers/moe/xmoe.py:143-162 in ONE launch that reads
+ * x once, followed by a one-workgroup patch launch that returns at once unless a row was non-finite.  With R = E / 2:
+ *   reduced[T,R] (dtype) = x[T,D] @ w_red[R,D]^T: the bits csmoe_gate_logits gives (a layer with `sel_bias` uses the separate entries);
+ *   logits[T,E] (dtype)  = (reduced / max(||reduced||, eps)) @ emb[E,R]^T, fp32 over ascending r (operands rounded to bf16 first
+ *                          under CSMOE_COS_OPER_BF16); `emb` is the fp32 copy of the (already renormalised) expert embeddings;
+ *   p[T,E] fp32, idx[T,K], w[T,K] = csmoe_router_select(logits, SEL_TEMP_SOFTMAX_TOPK, flags & 3, temperature): identical bits;
+ *   block_hist (nullable) as csmoe_gate_select (rows per block: csmoe_gate_select_rows()).
+ * A row whose logits are not finite is routed from E equal values (experts 0..K-1, weights 1/K); its stored logits become the
+ * smallest finite logit of the whole tensor (what `_make_finite` assigns) in the patch launch.  `work` holds
+ * csmoe_cosine_select_work_ints(T) int32: [0] = number of non-finite rows of this call (written by the patch launch), the rest
+ * per-workgroup scratch.  No host synchronisation.
+ * Shapes it takes: csmoe_cosine_select_ok(...) = 1 (bf16, E even, E <= 64, D % 8 == 0). */
+int csmoe_cosine_select_ok(int T, int D, int E, int K, int dtype);
+int64_t csmoe_cosine_select_work_ints(int T);
+int csmoe_cosine_select(const void* x, const void* w_red, const float* emb, int T, int D, int E, int K,
+                        int flags, float temperature, float eps, int dtype, void* reduced, void* logits, float* p, int32_t* idx,
+                        float* w, int32_t* block_hist, int32_t* work, csmoe_stream_t stream);
+
+/* backward of the row half of csmoe_cosine_select (autograd of the same reference lines, rounding where its ops round):
+ * dw[T,K] fp32, dp[T,E] fp32 (nullable: the balance loss), dlogits[T,E] `dtype` (nullable: z-loss / entropy balance) ->
+ * d_reduced[T,R] (dtype) and d_emb[E,R] fp32 (gradient w.r.t. `emb`; under CSMOE_COS_OPER_BF16 the caller rounds it to bf16 as the
+ * reference's bf16 matmul backward does).  `part` holds csmoe_cosine_select_bwd_parts(T) * E * R fp32 partial tables summed in a
+ * fixed order (a second launch): deterministic, no floating-point atomics.  `logits` are the stored (patched) ones: rows that were
+ * non-finite carry E equal logits and route uniformly, exactly as the reference's. */
+int csmoe_cosine_select_bwd_parts(int T);
+int csmoe_cosine_select_bwd(const void* reduced, const float* emb, const void* logits, const int32_t* idx, const float* w,
+                            const float* dw, const float* dp, const void* dlogits, int T, int E, int K, int flags,
+                            float temperature, float eps, int dtype, void* d_reduced, float* d_emb, float* part,
+                            csmoe_stream_t stream);
 
 /* aff[m] = (sum_j partial[m, j]) / D in `aff_dtype` (bf16 or fp32): closes CSMOE_EPI_SOFTPLUS_ROWSUM; `aff` is strided
  * (element stride `aff_stride`) so that expert e's column of an affinity matrix [T, E] is written in place. */

@@ -1,6 +1,13 @@
 #!/usr/bin/env python3
-"""One-pass router (csmoe_gate_select) against gate GEMM + router_select + counting pass at the headline token count.
-usage (GPU box): python tools/router_bench.py"""
+"""One-pass router (csmoe_gate_select) against gate GEMM + router_select + counting pass at the headline token count, and the
+one-pass XMoE cosine router (csmoe_cosine_select) against the torch-op form of the same gate and against csmoe_gate_select at the
+same T and D (it streams the same bytes).
+usage (GPU box): python tools/router_bench.py [linear|cosine|all] [rounds [iters]]   (rounds / iters: the cosine case)
+
+What the event times are: every candidate is called through its Python entry, which allocates its outputs (five to seven
+torch.empty) and launches; the torch-op gate is about a dozen eager launches per call.  The figures are therefore the cost of a
+call as a layer pays it -- GPU time plus whatever of the host's dispatch the GPU cannot hide -- not kernel durations.  For those,
+run the same command under a kernel trace with statistics, in a run of its own, and read the per-kernel averages."""
 import os
 import sys
 
@@ -23,7 +30,46 @@ def timed(fn, iters=20):
     return a.elapsed_time(b) / iters * 1e3
 
 
+def cosine(rounds=3, iters=500):
+    """T = 32 768, D = 4096, E = 64, K = 2, bf16, the flags of the pretrain stack under bf16 autocast.  The candidates alternate
+    inside every round, so that a drift of the machine shows up as spread between rounds rather than as a difference."""
+    from competesmoe_amd.functional import cosine_route_unfused
+    dev = "cuda"
+    T, D, E, K = 32768, 4096, 64, 2
+    flags = L.COS_OPER_BF16
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn(T, D, device=dev, generator=g).to(torch.bfloat16)
+    wr = (torch.randn(E // 2, D, device=dev, generator=g) * D ** -0.5).to(torch.bfloat16)
+    wg = (torch.randn(E, D, device=dev, generator=g) * D ** -0.5).to(torch.bfloat16)
+    emb = torch.randn(E, E // 2, device=dev, generator=g)
+    emb = (emb * (1.5 / emb.norm(dim=-1, keepdim=True))).contiguous()
+    red, lg, p, idx, w, _ = ops.cosine_select(x, wr, emb, K, flags)
+    dw, dp = torch.randn(T, K, device=dev, generator=g), torch.randn(T, E, device=dev, generator=g)
+    dl = torch.randn(T, E, device=dev, generator=g).to(torch.bfloat16)
+    cands = {
+        "cosine_select (one pass + patch launch)": lambda: ops.cosine_select(x, wr, emb, K, flags),
+        "torch-op gate (GateLogits + normalize + matmul + make_finite + router_select)":
+            lambda: cosine_route_unfused(x, wr, None, emb, K, flags),
+        "gate_select (linear router, same T and D)": lambda: ops.gate_select(x, wg, K, L.SEL_SOFTMAX, True),
+        "cosine_select_bwd (row kernel + d_emb sum)": lambda: ops.cosine_select_bwd(red, emb, lg, idx, w, dw, dp, dl, K, flags),
+    }
+    gb = T * D * 2 / 1e9
+    times = {k: [] for k in cands}
+    with torch.no_grad():
+        for _ in range(rounds):
+            for k, fn in cands.items():
+                times[k].append(timed(fn, iters))
+    for k, v in times.items():
+        rate = f" ({gb / min(v) * 1e6:.0f} GB/s of x at the best round)" if "bwd" not in k else ""
+        print(f"T={T} D={D} E={E} K={K} {k}: " + " / ".join(f"{t:.1f}" for t in v) + f" us{rate}", flush=True)
+
+
 def main():
+    which = sys.argv[1] if len(sys.argv) > 1 else "all"
+    if which in ("cosine", "all"):
+        cosine(*(int(a) for a in sys.argv[2:4]))
+    if which == "cosine":
+        return
     dev = "cuda"
     for T, D, E, K in ((32768, 4096, 64, 2), (32768, 4096, 64, 8), (32768, 1024, 64, 2), (32768, 4096, 16, 2), (12800, 1152, 4, 2)):
         x = torch.randn(T, D, device=dev).to(torch.bfloat16)
