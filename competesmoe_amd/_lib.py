@@ -21,6 +21,7 @@ F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_GELU_TANH, ACT_SILU, ACT_QUICK_GELU = 0, 1, 2, 3, 4, 5
 SEL_SOFTMAX, SEL_RAW, SEL_TOPK_SOFTMAX, SEL_SIGMOID, SEL_TOPK_SIGMOID, SEL_TEMP_SOFTMAX_TOPK = 0, 1, 2, 3, 4, 5
 TEMP_P_BF16, TEMP_W_BF16, COS_OPER_BF16 = 1, 2, 4      # rounding points of the cosine router (include/csmoe.h)
+COS_NORM_THETA, COS_NORM_BF16 = 8, 16                  # the perturbed-cosine normalisation reduced / (norm + theta), bf16 norm
 COMBINE_SEQ, COMBINE_DOT, COMBINE_SEQ_RW = 0, 1, 2
 B_NK, B_KN = 0, 1
 EPI_PLAIN, EPI_BIAS, EPI_BIAS_ACT, EPI_ACTGRAD, EPI_ROUND_BIAS32_ACT, EPI_SOFTPLUS_ROWSUM, EPI_SOFTPLUS_GRAD = 0, 1, 2, 3, 4, 5, 6

@@ -261,7 +261,8 @@ int csmoe_cosine_select(const void* x, const void* w_red, const float* emb, int 
                         float eps, int dtype, void* reduced, void* logits, float* p, int32_t* idx, float* w, int32_t* block_hist,
                         int32_t* work, csmoe_stream_t stream) {
   CSMOE_CHECK_ARG(T >= 0 && D > 0 && E > 0 && K > 0 && K <= E, "cosine_select: bad shape T=%d D=%d E=%d K=%d", T, D, E, K);
-  CSMOE_CHECK_ARG(flags >= 0 && flags <= 7 && temperature > 0.f && eps > 0.f, "cosine_select: bad flags %d / temperature / eps", flags);
+  CSMOE_CHECK_ARG(flags >= 0 && flags <= 31 && (!(flags & CSMOE_COS_NORM_BF16) || (flags & CSMOE_COS_NORM_THETA)) && temperature > 0.f &&
+                      eps > 0.f, "cosine_select: bad flags %d / temperature / eps", flags);
   CSMOE_CHECK_ARG(k_cosine_select_ok(T, D, E, K, dtype, x, w_red),
                   "cosine_select: needs bf16, E even and <= 64, D a multiple of 8, 16-byte aligned operands (csmoe_cosine_select_ok)");
   CSMOE_CHECK_ARG(work, "cosine_select: null work buffer");
@@ -277,7 +278,8 @@ int csmoe_cosine_select_bwd(const void* reduced, const float* emb, const void* l
                             float eps, int dtype, void* d_reduced, float* d_emb, float* part, csmoe_stream_t stream) {
   CSMOE_CHECK_ARG(dtype == CSMOE_BF16, "cosine_select_bwd: bf16 only (dtype %d)", dtype);
   CSMOE_CHECK_ARG(T >= 0 && E >= 2 && E <= 64 && E % 2 == 0 && K > 0 && K <= E, "cosine_select_bwd: bad shape T=%d E=%d K=%d", T, E, K);
-  CSMOE_CHECK_ARG(flags >= 0 && flags <= 7 && temperature > 0.f && eps > 0.f, "cosine_select_bwd: bad flags %d / temperature / eps", flags);
+  CSMOE_CHECK_ARG(flags >= 0 && flags <= 31 && (!(flags & CSMOE_COS_NORM_BF16) || (flags & CSMOE_COS_NORM_THETA)) && temperature > 0.f &&
+                      eps > 0.f, "cosine_select_bwd: bad flags %d / temperature / eps", flags);
   CSMOE_CHECK_ARG(emb && d_emb && part && (T == 0 || (reduced && logits && idx && w && d_reduced)), "cosine_select_bwd: null pointer");
   return k_cosine_select_bwd(reduced, emb, logits, idx, w, dw, dp, dlogits, T, E, K, flags, temperature, eps, d_reduced, d_emb, part,
                              (hipStream_t)stream);

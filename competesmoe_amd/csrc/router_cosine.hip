@@ -15,6 +15,9 @@
 // finite logit of the tensor, i.e. routes the row from E equal values.  The row is routed that way here (experts 0..K-1, weights
 // 1/K) without knowing the minimum; every workgroup leaves the minimum of its finite logits and its count of such rows, and a
 // one-workgroup patch launch that returns at once when the counts are all zero rewrites the stored logits of those rows.
+// Second normalisation (CSMOE_COS_NORM_THETA, the perturbed-cosine router `smoe_perturbed`, moe_model/model/moe/smoe_perturbed.py:
+// 102): the row is divided by ||reduced|| + theta, no clamp (`eps` carries theta); under CSMOE_COS_NORM_BF16 the norm and the sum
+// are bf16 tensors, as in a bf16 module without autocast.  A template parameter: the XMoE instantiations hold none of its code.
 #include "router_select.h"
 
 namespace {
@@ -37,7 +40,15 @@ __device__ __forceinline__ float g16_sum(float v) {
 }
 
 // The row half of both kernels: `reduced` of this wave's 16 rows lies in LDS ([16][RC_LR] per wave, fp32 values of the bf16 results).
-template <bool K2>
+// ||reduced|| + theta of CSMOE_COS_NORM_THETA from the fp32 sum of squares; `nrm` receives the norm the autograd sees.
+__device__ __forceinline__ float theta_denom(float ss, float theta, bool norm_bf16, float& nrm) {
+  nrm = sqrtf(ss);
+  if (!norm_bf16) return nrm + theta;
+  nrm = (float)(bf16)nrm;                                      // `mat1.norm()` of a bf16 tensor: an fp32 sum rounded once
+  return (float)(bf16)(nrm + theta);                           // `+ theta` on that bf16 tensor
+}
+
+template <bool K2, bool THETA>
 __device__ __forceinline__ void cosine_row_half(char* smem, const float* __restrict__ emb, int T, int E, int K_rt, int flags,
                                                 float temperature, float eps, bf16* __restrict__ reduced, bf16* __restrict__ logits,
                                                 float* __restrict__ p, int32_t* __restrict__ idx, float* __restrict__ w,
@@ -76,7 +87,9 @@ __device__ __forceinline__ void cosine_row_half(char* smem, const float* __restr
     if (live && i16 + 16 < R) reduced[tt * R + i16 + 16] = (bf16)x1;
     // ||reduced||: elements l and l + 16 inside the lane, then the 16-lane tree (xor 8, 4, 2, 1)
     const float ss = g16_sum(x0 * x0 + x1 * x1);
-    const float denom = fmaxf(sqrtf(ss), eps);
+    float denom, nrm_;
+    if constexpr (THETA) denom = theta_denom(ss, eps, flags & CSMOE_COS_NORM_BF16, nrm_);
+    else denom = fmaxf(sqrtf(ss), eps);
     float m0 = x0 / denom, m1 = x1 / denom;
     if (oper_bf16) { m0 = (float)(bf16)m0; m1 = (float)(bf16)m1; }
     if (i16 < R) mr[i16] = m0;
@@ -138,7 +151,7 @@ __device__ __forceinline__ void cosine_row_half(char* smem, const float* __restr
 // per row, lane l takes the 16-byte pieces l, l + 64, ... of the row, fp32 products added in element order, then the wave
 // butterfly -- so that `reduced` carries that entry's bits here too; an MFMA tile would be 3/4 empty.  A wave owns the same 16 rows
 // of the same 64-row block as in the MFMA kernel (one block histogram contract), four rows in flight at a time.
-template <bool K2>
+template <bool K2, bool THETA>
 __global__ void __launch_bounds__(64 * RC_WAVES) cosine_select_small_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wr,
                                                                             const float* __restrict__ emb, int T, int D, int E, int K_rt,
                                                                             int flags, float temperature, float eps,
@@ -178,11 +191,11 @@ __global__ void __launch_bounds__(64 * RC_WAVES) cosine_select_small_kernel(cons
         if (lane == 0 && e < R) lrow[(r0 + q) * RC_LR + e] = (float)(bf16)sum;
       }
   }
-  cosine_row_half<K2>(smem, emb, T, E, K_rt, flags, temperature, eps, reduced, logits, p, idx, w, block_hist, work);
+  cosine_row_half<K2, THETA>(smem, emb, T, E, K_rt, flags, temperature, eps, reduced, logits, p, idx, w, block_hist, work);
 }
 
 // work[0]: non-finite rows of the call (patch launch); work[2 + b]: count of workgroup b; work[2 + nb + b]: its finite minimum (float bits)
-template <int NE, bool K2>
+template <int NE, bool K2, bool THETA>
 __global__ void __launch_bounds__(64 * RC_WAVES) cosine_select_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wr,
                                                                       const float* __restrict__ emb, int T, int D, int E, int K_rt,
                                                                       int flags, float temperature, float eps,
@@ -265,7 +278,7 @@ __global__ void __launch_bounds__(64 * RC_WAVES) cosine_select_kernel(const bf16
   for (int c = 0; c < NE; ++c)
 #pragma unroll
     for (int j = 0; j < 4; ++j) lrow[(4 * g + j) * RC_LR + c * 16 + i16] = (float)(bf16)acc[c][j];
-  cosine_row_half<K2>(smem, emb, T, E, K_rt, flags, temperature, eps, reduced, logits, p, idx, w, block_hist, work);
+  cosine_row_half<K2, THETA>(smem, emb, T, E, K_rt, flags, temperature, eps, reduced, logits, p, idx, w, block_hist, work);
 }
 
 // One workgroup after every cosine_select launch: sums the counts; nothing else to do when the sum is zero.
@@ -314,13 +327,15 @@ __global__ void __launch_bounds__(256) cosine_patch_kernel(bf16* __restrict__ lo
 // in their order: softmax over K, top-K scatter (+ d p of the losses), the fp32 softmax with its own unrounded output, the cast and
 // the division by the temperature in bf16, (+ d logits of the losses, added in bf16 as the engine adds two bf16 gradients), the
 // cosine product (fp32; its operand gradients rounded to bf16 under CSMOE_COS_OPER_BF16), F.normalize (the clamp blocks the norm's
-// branch where the norm is below eps: d reduced = d m / eps there), rounded to bf16 at `reduced`.
+// branch where the norm is below eps: d reduced = d m / eps there), rounded to bf16 at `reduced`.  Under CSMOE_COS_NORM_THETA the
+// last step is the division by ||v|| + theta instead: two bf16 gradients of `reduced` (the cast and the norm) added in bf16.
 // d emb[e][r] = sum_t d cos[t][e] m[t][r]: each lane keeps its 4 x 32 entries in registers over the rows its group visits (ascending),
 // the 16 groups of a workgroup are added in group order through LDS, and workgroup b writes partial table b; cosine_demb_kernel
 // adds the tables in ascending b.  No atomics: the same bits on every run.
 constexpr int CB_GROUPS = 16;                                  // row groups per workgroup (256 threads)
 constexpr int CB_MAX_PARTS = 256;
 
+template <bool THETA>
 __global__ void __launch_bounds__(256) cosine_select_bwd_kernel(const bf16* __restrict__ reduced, const float* __restrict__ emb,
                                                                 const bf16* __restrict__ logits, const int32_t* __restrict__ idx,
                                                                 const float* __restrict__ w, const float* __restrict__ dw,
@@ -333,6 +348,7 @@ __global__ void __launch_bounds__(256) cosine_select_bwd_kernel(const bf16* __re
   const int R = E >> 1;
   const int tid = threadIdx.x, grp = tid >> 4, l16 = tid & 15;
   const bool oper_bf16 = flags & CSMOE_COS_OPER_BF16, pb = flags & CSMOE_TEMP_P_BF16, wb = flags & CSMOE_TEMP_W_BF16;
+  const bool norm_bf16 = THETA && (flags & CSMOE_COS_NORM_BF16);
   for (int i = tid; i < E * R; i += 256) {
     const float v = emb[i];
     semb[(i / R) * RC_LR + (i % R)] = oper_bf16 ? (float)(bf16)v : v;
@@ -400,8 +416,11 @@ __global__ void __launch_bounds__(256) cosine_select_bwd_kernel(const bf16* __re
       dc[j] = (live && row_ok && e < E) ? d : 0.f;
       sd_[e] = dc[j];
     }
-    const float denom = fmaxf(nrm, eps);
+    float denom, nrm_t = nrm;                                  // nrm_t: the norm as the reference's tensor holds it (THETA)
+    if constexpr (THETA) denom = theta_denom(ss, eps, norm_bf16, nrm_t);
+    else denom = fmaxf(nrm, eps);
     float m0 = x0 / denom, m1 = x1 / denom;
+    const float q0 = m0, q1 = m1;                              // the fp32 quotient: what the division's backward multiplies by
     if (oper_bf16) { m0 = (float)(bf16)m0; m1 = (float)(bf16)m1; }
     sm_[l16] = l16 < R ? m0 : 0.f;
     sm_[l16 + 16] = l16 + 16 < R ? m1 : 0.f;
@@ -424,14 +443,29 @@ __global__ void __launch_bounds__(256) cosine_select_bwd_kernel(const bf16* __re
     if (l16 >= R) dm0 = 0.f;
     if (l16 + 16 >= R) dm1 = 0.f;
     if (oper_bf16) { dm0 = (float)(bf16)dm0; dm1 = (float)(bf16)dm1; }
-    // ---- F.normalize: m = v / clamp_min(||v||, eps)
     float dx0 = dm0 / denom, dx1 = dm1 / denom;
-    if (!row_ok) { m0 = 0.f; m1 = 0.f; }
-    if (row_ok && nrm >= eps) {
-      const float dd = g16_sum(dm0 * x0 + dm1 * x1);      // uniform branch inside the 16-lane group: the rotation stays inside it
-      const float dden = -dd / (denom * denom);
-      dx0 += dden * (x0 / nrm);
-      dx1 += dden * (x1 / nrm);
+    if constexpr (THETA) {
+      // ---- m = v.float() / (||v|| + theta): `reduced` is used twice and the engine adds two bf16 gradients.  Stream 1, the
+      // `.float()` cast, is d m / den rounded to bf16.  Stream 2, the norm: d den = sum_r -(d m_r (m_r / den)), a bf16 tensor under
+      // NORM_BF16 like den itself; the norm's backward d den (v / n) then runs in bf16, else in fp32 with one rounding at the
+      // autocast cast; it is masked where n == 0.
+      dx0 = (float)(bf16)dx0; dx1 = (float)(bf16)dx1;
+      float dden = g16_sum(-(dm0 * (q0 / denom)) - dm1 * (q1 / denom));
+      if (norm_bf16) dden = (float)(bf16)dden;
+      if (nrm_t != 0.f) {
+        float u0 = x0 / nrm_t, u1 = x1 / nrm_t;
+        if (norm_bf16) { u0 = (float)(bf16)u0; u1 = (float)(bf16)u1; }
+        dx0 += (float)(bf16)(dden * u0);
+        dx1 += (float)(bf16)(dden * u1);
+      }
+    } else {
+      // ---- F.normalize: m = v / clamp_min(||v||, eps)
+      if (row_ok && nrm >= eps) {
+        const float dd = g16_sum(dm0 * x0 + dm1 * x1);    // uniform branch inside the 16-lane group: the rotation stays inside it
+        const float dden = -dd / (denom * denom);
+        dx0 += dden * (x0 / nrm);
+        dx1 += dden * (x1 / nrm);
+      }
     }
     if (!row_ok) { dx0 = 0.f; dx1 = 0.f; }
     if (live && l16 < R) d_reduced[tt * R + l16] = (bf16)dx0;
@@ -480,18 +514,24 @@ int k_cosine_select(const void* x, const void* wr, const float* emb, int T, int 
     const int ne = (E / 2 + 15) / 16;
     const dim3 grid(nb), block(64 * RC_WAVES);
     const size_t lds = std::max<size_t>((size_t)2 * ne * 16 * RC_LD * 2, (size_t)RC_TAIL_FLOATS * 4);
-#define RC_LAUNCH(NE, K2)                                                                                                        \
-  hipLaunchKernelGGL((cosine_select_kernel<NE, K2>), grid, block, lds, st, (const bf16*)x, (const bf16*)wr, emb, T, D, E, K, flags,  \
-                     temperature, eps, (bf16*)reduced, (bf16*)logits, p, idx, w, block_hist, work)
-    if (E <= 8) {
-      if (K == 2) hipLaunchKernelGGL((cosine_select_small_kernel<true>), grid, block, (size_t)RC_TAIL_FLOATS * 4, st, (const bf16*)x,
-                                     (const bf16*)wr, emb, T, D, E, K, flags, temperature, eps, (bf16*)reduced, (bf16*)logits, p, idx, w,
-                                     block_hist, work);
-      else        hipLaunchKernelGGL((cosine_select_small_kernel<false>), grid, block, (size_t)RC_TAIL_FLOATS * 4, st, (const bf16*)x,
-                                     (const bf16*)wr, emb, T, D, E, K, flags, temperature, eps, (bf16*)reduced, (bf16*)logits, p, idx, w,
-                                     block_hist, work);
-    } else if (ne == 1) { if (K == 2) RC_LAUNCH(1, true); else RC_LAUNCH(1, false); }
-    else         { if (K == 2) RC_LAUNCH(2, true); else RC_LAUNCH(2, false); }
+    const bool theta = flags & CSMOE_COS_NORM_THETA;
+#define RC_LAUNCH(NE, K2, TH)                                                                                                      \
+  hipLaunchKernelGGL((cosine_select_kernel<NE, K2, TH>), grid, block, lds, st, (const bf16*)x, (const bf16*)wr, emb, T, D, E, K,     \
+                     flags, temperature, eps, (bf16*)reduced, (bf16*)logits, p, idx, w, block_hist, work)
+#define RC_LAUNCH_SMALL(K2, TH)                                                                                                    \
+  hipLaunchKernelGGL((cosine_select_small_kernel<K2, TH>), grid, block, (size_t)RC_TAIL_FLOATS * 4, st, (const bf16*)x,              \
+                     (const bf16*)wr, emb, T, D, E, K, flags, temperature, eps, (bf16*)reduced, (bf16*)logits, p, idx, w, block_hist,  \
+                     work)
+#define RC_PICK(LAUNCH, ...)                                                                                                       \
+  do {                                                                                                                             \
+    if (theta) { if (K == 2) LAUNCH(__VA_ARGS__ true, true); else LAUNCH(__VA_ARGS__ false, true); }                               \
+    else       { if (K == 2) LAUNCH(__VA_ARGS__ true, false); else LAUNCH(__VA_ARGS__ false, false); }                             \
+  } while (0)
+    if (E <= 8) RC_PICK(RC_LAUNCH_SMALL, );
+    else if (ne == 1) RC_PICK(RC_LAUNCH, 1, );
+    else RC_PICK(RC_LAUNCH, 2, );
+#undef RC_PICK
+#undef RC_LAUNCH_SMALL
 #undef RC_LAUNCH
     CSMOE_CHECK_LAUNCH("cosine_select");
   }
@@ -508,8 +548,12 @@ int k_cosine_select_bwd(const void* reduced, const float* emb, const void* logit
   const int nparts = k_cosine_select_bwd_parts(T);
   const int n = E * (E / 2);
   if (T > 0) {
-    hipLaunchKernelGGL(cosine_select_bwd_kernel, dim3(nparts), dim3(256), 0, st, (const bf16*)reduced, emb, (const bf16*)logits, idx, w,
-                       dw, dp, (const bf16*)dlogits, T, E, K, flags, temperature, eps, (bf16*)d_reduced, part);
+    if (flags & CSMOE_COS_NORM_THETA)
+      hipLaunchKernelGGL(cosine_select_bwd_kernel<true>, dim3(nparts), dim3(256), 0, st, (const bf16*)reduced, emb, (const bf16*)logits,
+                         idx, w, dw, dp, (const bf16*)dlogits, T, E, K, flags, temperature, eps, (bf16*)d_reduced, part);
+    else
+      hipLaunchKernelGGL(cosine_select_bwd_kernel<false>, dim3(nparts), dim3(256), 0, st, (const bf16*)reduced, emb, (const bf16*)logits,
+                         idx, w, dw, dp, (const bf16*)dlogits, T, E, K, flags, temperature, eps, (bf16*)d_reduced, part);
     CSMOE_CHECK_LAUNCH("cosine_select_bwd");
   }
   hipLaunchKernelGGL(cosine_demb_kernel, dim3((n + 255) / 256), dim3(256), 0, st, part, T > 0 ? nparts : 0, n, d_emb);

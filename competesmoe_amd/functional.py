@@ -283,7 +283,9 @@ class CosineSelect(torch.autograd.Function):
     143-162).  Returns (logits, p fp32 holding the values rounded as `flags` say, idx int32, w fp32).  `flags`: _lib.TEMP_P_BF16 |
     TEMP_W_BF16 | COS_OPER_BF16, the reference's rounding points (include/csmoe.h).  `emb` is the parameter AFTER its in-place
     renormalisation; its gradient is the gradient w.r.t. those values.  Backward: one row kernel through selection, softmax, cosine
-    product and normalisation (csmoe_cosine_select_bwd, deterministic d emb), then the two gate products of GateLogits.backward."""
+    product and normalisation (csmoe_cosine_select_bwd, deterministic d emb), then the two gate products of GateLogits.backward.
+    With COS_NORM_THETA in `flags` it is the perturbed-cosine router (`smoe_perturbed`): the row is reduced / (norm + theta), `eps`
+    carries theta; COS_NORM_BF16 makes norm and sum bf16 tensors (a bf16 module without autocast)."""
 
     @staticmethod
     def forward(ctx, x2, expert_sel, emb, K: int, flags: int, temperature: float = 0.3, eps: float = 1e-4):
@@ -337,7 +339,8 @@ def make_finite(scores: torch.Tensor) -> torch.Tensor:
 def cosine_route_unfused(x2, expert_sel, sel_bias, emb, K: int, flags: int, temperature: float = 0.3, eps: float = 1e-4):
     """The same router where the one-pass kernel does not take the shape (fp32, E > 64, a `sel_bias`, CSMOE_FUSED_ROUTER=0): the
     reduction is the gate kernel (GateLogits), the [T, E/2]- and [T, E]-sized cosine math torch ops placed as `flags` say, the
-    selection the router kernel with CSMOE_SEL_TEMP_SOFTMAX_TOPK.  Returns (logits, p, idx, w) like CosineSelect.
+    selection the router kernel with CSMOE_SEL_TEMP_SOFTMAX_TOPK.  Returns (logits, p, idx, w) like CosineSelect, the
+    COS_NORM_THETA normalisation included.
 
     Known deviation: `sel_bias` is added to the reduction AFTER the gate kernel has rounded it to the compute dtype, and the sum is
     rounded again; F.linear(x, expert_sel, sel_bias) adds it to the fp32 accumulator and rounds once.  In fp32 (the only captured
@@ -347,7 +350,11 @@ def cosine_route_unfused(x2, expert_sel, sel_bias, emb, K: int, flags: int, temp
     with torch.autocast("cuda", enabled=False):
         if sel_bias is not None:
             reduced = reduced + sel_bias.to(reduced.dtype)
-        m = torch.nn.functional.normalize(reduced.float(), p=2.0, dim=-1, eps=eps)
+        if flags & L.COS_NORM_THETA:        # smoe_perturbed: `eps` is theta; the norm in reduced.dtype or, as under autocast, in fp32
+            nrm = (reduced if flags & L.COS_NORM_BF16 else reduced.float()).norm(p=2, dim=-1, keepdim=True)
+            m = reduced.float() / (nrm + eps)
+        else:
+            m = torch.nn.functional.normalize(reduced.float(), p=2.0, dim=-1, eps=eps)
         embf = emb.float()
         if flags & L.COS_OPER_BF16:
             cos = torch.matmul(m.to(torch.bfloat16), embf.to(torch.bfloat16).transpose(0, 1))

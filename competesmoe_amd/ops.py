@@ -176,7 +176,9 @@ def cosine_select_ok(x2: torch.Tensor, w_red: torch.Tensor, E: int, K: int) -> b
 def cosine_select(x2: torch.Tensor, w_red: torch.Tensor, emb: torch.Tensor, K: int, flags: int, temperature: float = 0.3,
                   eps: float = 1e-4, want_hist: bool = True):
     """XMoE's router in one launch that reads x2 once (+ the one-workgroup patch launch): (reduced [T,R], logits [T,E], p [T,E] fp32,
-    idx [T,K] int32, w [T,K] fp32, status [1] int32 = number of non-finite rows of this call).  `emb`: fp32 [E,R], renormalised."""
+    idx [T,K] int32, w [T,K] fp32, status [1] int32 = number of non-finite rows of this call).  `emb`: fp32 [E,R], renormalised.
+    `flags` & COS_NORM_THETA: the perturbed-cosine normalisation reduced / (norm + theta) with theta in `eps`; & COS_NORM_BF16: that
+    norm and sum as bf16 tensors (include/csmoe.h)."""
     _need_cuda(x2, w_red, emb)
     _rows("cosine_select", x2, w_red, emb)
     if emb.dtype != torch.float32:
@@ -203,7 +205,8 @@ def cosine_select(x2: torch.Tensor, w_red: torch.Tensor, emb: torch.Tensor, K: i
 
 def cosine_select_bwd(reduced, emb, logits, idx, w, dw, dp, dlogits, K: int, flags: int, temperature: float = 0.3, eps: float = 1e-4):
     """(d_reduced [T,R] in reduced.dtype, d_emb [E,R] fp32) of csmoe_cosine_select_bwd; dw / dp fp32 or None, dlogits in
-    logits.dtype or None.  Deterministic (fixed-order partial tables)."""
+    logits.dtype or None.  Deterministic (fixed-order partial tables).  `flags` / `eps` as given to cosine_select (under
+    COS_NORM_THETA `eps` is theta and d_reduced the bf16 sum of the cast's and the norm's bf16 gradients)."""
     _rows("cosine_select_bwd", reduced, emb, logits, idx, w, dw, dp, dlogits)
     T, R = reduced.shape
     E = emb.shape[0]

@@ -47,7 +47,9 @@ enum {
 enum {
   CSMOE_TEMP_P_BF16 = 1,    /* p is cast to bf16 before the top-K (`.to(x.dtype)` of a bf16 module)                          */
   CSMOE_TEMP_W_BF16 = 2,    /* the softmax over the K keys is a bf16 tensor op                                                */
-  CSMOE_COS_OPER_BF16 = 4   /* the cosine product's operands are rounded to bf16 (`matmul` under bf16 autocast)              */
+  CSMOE_COS_OPER_BF16 = 4,  /* the cosine product's operands are rounded to bf16 (`matmul` under bf16 autocast)              */
+  CSMOE_COS_NORM_THETA = 8, /* perturbed cosine: the row is reduced / (||reduced|| + theta), no clamp; `eps` carries theta    */
+  CSMOE_COS_NORM_BF16 = 16  /* with NORM_THETA: the norm and `norm + theta` are bf16 tensors (a bf16 module without autocast) */
 };
 
 /* Combine rounding rule. */
@@ -170,6 +172,9 @@ int csmoe_gate_select(const void* x, const void* w_gate, int T, int D, int E, in
  *   reduced[T,R] (dtype) = x[T,D] @ w_red[R,D]^T: the bits csmoe_gate_logits gives (a layer with `sel_bias` uses the separate entries);
  *   logits[T,E] (dtype)  = (reduced / max(||reduced||, eps)) @ emb[E,R]^T, fp32 over ascending r (operands rounded to bf16 first
  *                          under CSMOE_COS_OPER_BF16); `emb` is the fp32 copy of the (already renormalised) expert embeddings;
+ *                          under CSMOE_COS_NORM_THETA (`smoe_perturbed`) the row is reduced / (||reduced|| + eps) instead, `eps`
+ *                          carrying theta, no clamp: a zero row gives E zero logits; with CSMOE_COS_NORM_BF16 the norm and the sum
+ *                          are rounded to bf16 (n = bf16(sqrt(sum v^2)), den = bf16(n + theta)), the division stays fp32;
  *   p[T,E] fp32, idx[T,K], w[T,K] = csmoe_router_select(logits, SEL_TEMP_SOFTMAX_TOPK, flags & 3, temperature): identical bits;
  *   block_hist (nullable) as csmoe_gate_select (rows per block: csmoe_gate_select_rows()).
  * A row whose logits are not finite is routed from E equal values (experts 0..K-1, weights 1/K); its stored logits become the
@@ -188,7 +193,9 @@ int csmoe_cosine_select(const void* x, const void* w_red, const float* emb, int 
  * d_reduced[T,R] (dtype) and d_emb[E,R] fp32 (gradient w.r.t. `emb`; under CSMOE_COS_OPER_BF16 the caller rounds it to bf16 as the
  * reference's bf16 matmul backward does).  `part` holds csmoe_cosine_select_bwd_parts(T) * E * R fp32 partial tables summed in a
  * fixed order (a second launch): deterministic, no floating-point atomics.  `logits` are the stored (patched) ones: rows that were
- * non-finite carry E equal logits and route uniformly, exactly as the reference's. */
+ * non-finite carry E equal logits and route uniformly, exactly as the reference's.  Under CSMOE_COS_NORM_THETA d_reduced is the
+ * bf16 sum of two bf16 gradients, as the engine adds them: d m / den (the `.float()` cast) and the norm's d den * (v / n), zero
+ * where n == 0, computed in bf16 under CSMOE_COS_NORM_BF16 and in fp32 with one rounding otherwise. */
 int csmoe_cosine_select_bwd_parts(int T);
 int csmoe_cosine_select_bwd(const void* reduced, const float* emb, const void* logits, const int32_t* idx, const float* w,
                             const float* dw, const float* dp, const void* dlogits, int T, int E, int K, int flags,

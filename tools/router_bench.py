@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """One-pass router (csmoe_gate_select) against gate GEMM + router_select + counting pass at the headline token count, and the
 one-pass XMoE cosine router (csmoe_cosine_select) against the torch-op form of the same gate and against csmoe_gate_select at the
-same T and D (it streams the same bytes).
-usage (GPU box): python tools/router_bench.py [linear|cosine|all] [rounds [iters]]   (rounds / iters: the cosine case)
+same T and D (it streams the same bytes); `perturbed`: the same kernel in its CSMOE_COS_NORM_THETA mode (`smoe_perturbed`) against
+the XMoE mode of the same build and the torch-op gate.
+usage (GPU box): python tools/router_bench.py [linear|cosine|perturbed|all] [rounds [iters]]   (rounds / iters: the cosine cases)
 
 What the event times are: every candidate is called through its Python entry, which allocates its outputs (five to seven
 torch.empty) and launches; the torch-op gate is about a dozen eager launches per call.  The figures are therefore the cost of a
@@ -64,11 +65,56 @@ def cosine(rounds=3, iters=500):
         print(f"T={T} D={D} E={E} K={K} {k}: " + " / ".join(f"{t:.1f}" for t in v) + f" us{rate}", flush=True)
 
 
+def perturbed(rounds=3, iters=500):
+    """The shape and the method of `cosine`.  Flag sets 27 (the LLaVA bf16 module) and 12 (the pretrain stack under bf16 autocast)
+    of the perturbed normalisation, theta = 0.1; the XMoE launch of the same build (flags 4) reads the same bytes and is the
+    yardstick inside the run."""
+    from competesmoe_amd.functional import cosine_route_unfused
+    dev = "cuda"
+    T, D, E, K = 32768, 4096, 64, 2
+    theta = 0.1
+    f_llava = L.TEMP_P_BF16 | L.TEMP_W_BF16 | L.COS_NORM_THETA | L.COS_NORM_BF16
+    f_pre = L.COS_OPER_BF16 | L.COS_NORM_THETA
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn(T, D, device=dev, generator=g).to(torch.bfloat16)
+    wr = (torch.randn(E // 2, D, device=dev, generator=g) * D ** -0.5).to(torch.bfloat16)
+    emb = torch.randn(E, E // 2, device=dev, generator=g)
+    emb = (emb * (1.5 / (emb.norm(dim=-1, keepdim=True) + theta))).contiguous()
+    dw, dp = torch.randn(T, K, device=dev, generator=g), torch.randn(T, E, device=dev, generator=g)
+    dl = torch.randn(T, E, device=dev, generator=g).to(torch.bfloat16)
+    saved = {f: ops.cosine_select(x, wr, emb, K, f, 0.3, theta if f & L.COS_NORM_THETA else 1e-4) for f in (f_llava, f_pre, L.COS_OPER_BF16)}
+
+    def bwd(f, eps):
+        red, lg, _, idx, w, _ = saved[f]
+        return lambda: ops.cosine_select_bwd(red, emb, lg, idx, w, dw, dp, dl, K, f, 0.3, eps)
+    cands = {
+        f"cosine_select NORM_THETA flags {f_llava} (LLaVA bf16 module)": lambda: ops.cosine_select(x, wr, emb, K, f_llava, 0.3, theta),
+        f"cosine_select NORM_THETA flags {f_pre} (pretrain, bf16 autocast)": lambda: ops.cosine_select(x, wr, emb, K, f_pre, 0.3, theta),
+        "cosine_select xmoe flags 4 (same build)": lambda: ops.cosine_select(x, wr, emb, K, L.COS_OPER_BF16),
+        f"torch-op gate NORM_THETA flags {f_pre} (GateLogits + norm + div + matmul + make_finite + router_select)":
+            lambda: cosine_route_unfused(x, wr, None, emb, K, f_pre, 0.3, theta),
+        f"cosine_select_bwd NORM_THETA flags {f_llava}": bwd(f_llava, theta),
+        f"cosine_select_bwd NORM_THETA flags {f_pre}": bwd(f_pre, theta),
+        "cosine_select_bwd xmoe flags 4 (same build)": bwd(L.COS_OPER_BF16, 1e-4),
+    }
+    gb = T * D * 2 / 1e9
+    times = {k: [] for k in cands}
+    with torch.no_grad():
+        for _ in range(rounds):
+            for k, fn in cands.items():
+                times[k].append(timed(fn, iters))
+    for k, v in times.items():
+        rate = f" ({gb / min(v) * 1e6:.0f} GB/s of x at the best round)" if "bwd" not in k else ""
+        print(f"T={T} D={D} E={E} K={K} {k}: " + " / ".join(f"{t:.1f}" for t in v) + f" us{rate}", flush=True)
+
+
 def main():
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     if which in ("cosine", "all"):
         cosine(*(int(a) for a in sys.argv[2:4]))
-    if which == "cosine":
+    if which in ("perturbed", "all"):
+        perturbed(*(int(a) for a in sys.argv[2:4]))
+    if which in ("cosine", "perturbed"):
         return
     dev = "cuda"
     for T, D, E, K in ((32768, 4096, 64, 2), (32768, 4096, 64, 8), (32768, 1024, 64, 2), (32768, 4096, 16, 2), (12800, 1152, 4, 2)):
