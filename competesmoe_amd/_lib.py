@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("CSMOE_LIB") or os.path.join(_HERE, "lib", "libcsmoe_h
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_GELU_TANH, ACT_SILU, ACT_QUICK_GELU = 0, 1, 2, 3, 4, 5
 SEL_SOFTMAX, SEL_RAW, SEL_TOPK_SOFTMAX, SEL_SIGMOID, SEL_TOPK_SIGMOID, SEL_TEMP_SOFTMAX_TOPK = 0, 1, 2, 3, 4, 5
+SEL_SIGMOID_NORM = 6          # topk(sigmoid) -> w / K-sum without epsilon, `.to(x.dtype)` on the sum (include/csmoe.h)
 TEMP_P_BF16, TEMP_W_BF16, COS_OPER_BF16 = 1, 2, 4      # rounding points of the cosine router (include/csmoe.h)
 COS_NORM_THETA, COS_NORM_BF16 = 8, 16                  # the perturbed-cosine normalisation reduced / (norm + theta), bf16 norm
 COMBINE_SEQ, COMBINE_DOT, COMBINE_SEQ_RW = 0, 1, 2

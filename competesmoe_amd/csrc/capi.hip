@@ -205,7 +205,7 @@ int csmoe_router_select(const void* scores, int dtype, int T, int E, int K, int 
   CSMOE_CHECK_ARG(dtype_ok(dtype), "router_select: bad dtype %d", dtype);
   CSMOE_CHECK_ARG(T >= 0 && E > 0 && E <= 1024, "router_select: E=%d out of range (1..1024)", E);
   CSMOE_CHECK_ARG(K > 0 && K <= E && K <= 64, "router_select: K=%d out of range (1..min(E,64))", K);
-  CSMOE_CHECK_ARG(sel_mode >= 0 && sel_mode <= 5, "router_select: bad mode %d", sel_mode);
+  CSMOE_CHECK_ARG(sel_mode >= 0 && sel_mode <= 6, "router_select: bad mode %d", sel_mode);
   CSMOE_CHECK_ARG(sel_mode != CSMOE_SEL_TOPK_SIGMOID || sel_param != 0.f, "router_select: SEL_TOPK_SIGMOID needs a non-zero scale");
   CSMOE_CHECK_ARG(sel_mode != CSMOE_SEL_TEMP_SOFTMAX_TOPK || sel_param > 0.f, "router_select: SEL_TEMP_SOFTMAX_TOPK needs a positive temperature");
   if (T == 0) return CSMOE_OK;
@@ -218,7 +218,7 @@ int csmoe_router_select_bwd(const void* scores, int dtype, int T, int E, int K, 
                             void* dscores, csmoe_stream_t stream) {
   CSMOE_CHECK_ARG(dtype_ok(dtype), "router_select_bwd: bad dtype %d", dtype);
   CSMOE_CHECK_ARG(T >= 0 && E > 0 && E <= 1024 && K > 0 && K <= E && K <= 64, "router_select_bwd: bad shape");
-  CSMOE_CHECK_ARG(sel_mode >= 0 && sel_mode <= 5, "router_select_bwd: bad mode %d", sel_mode);
+  CSMOE_CHECK_ARG(sel_mode >= 0 && sel_mode <= 6, "router_select_bwd: bad mode %d", sel_mode);
   CSMOE_CHECK_ARG(sel_mode != CSMOE_SEL_TOPK_SIGMOID || sel_param != 0.f, "router_select_bwd: SEL_TOPK_SIGMOID needs a non-zero scale");
   CSMOE_CHECK_ARG(sel_mode != CSMOE_SEL_TEMP_SOFTMAX_TOPK || sel_param > 0.f, "router_select_bwd: SEL_TEMP_SOFTMAX_TOPK needs a positive temperature");
   if (T == 0) return CSMOE_OK;
@@ -294,7 +294,7 @@ int csmoe_gate_select_rows(void) { return k_gate_select_rows(); }
 int csmoe_gate_select(const void* x, const void* w_gate, int T, int D, int E, int K, int sel_mode, int round_sum_bf16, float sel_param,
                       int dtype, void* logits, float* softmax, int32_t* idx, float* w, int32_t* block_hist, csmoe_stream_t stream) {
   CSMOE_CHECK_ARG(T >= 0 && D > 0 && E > 0 && K > 0 && K <= E && K <= 64, "gate_select: bad shape T=%d D=%d E=%d K=%d", T, D, E, K);
-  CSMOE_CHECK_ARG(sel_mode >= 0 && sel_mode <= 4, "gate_select: bad mode %d", sel_mode);
+  CSMOE_CHECK_ARG((sel_mode >= 0 && sel_mode <= 4) || sel_mode == CSMOE_SEL_SIGMOID_NORM, "gate_select: bad mode %d", sel_mode);
   CSMOE_CHECK_ARG(sel_mode != CSMOE_SEL_TOPK_SIGMOID || sel_param != 0.f, "gate_select: SEL_TOPK_SIGMOID needs a non-zero scale");
   CSMOE_CHECK_ARG(k_gate_select_ok(T, D, E, K, dtype, x, w_gate),
                   "gate_select: needs bf16, E <= 64, D a multiple of 8, 16-byte aligned operands (csmoe_gate_select_ok)");

@@ -33,6 +33,11 @@ __global__ void __launch_bounds__(256) router_select_kernel(const void* scores, 
                          w + (int64_t)t * K);
     return;
   }
+  if (mode == CSMOE_SEL_SIGMOID_NORM) {
+    select_row_signorm<VPL>(s, lane, E, K, round_sum_bf16, dtype, softmax ? softmax + base : nullptr, idx + (int64_t)t * K,
+                            w + (int64_t)t * K);
+    return;
+  }
   select_row<VPL>(s, lane, E, K, mode, round_sum_bf16, sel_param, dtype, softmax ? softmax + base : nullptr, idx + (int64_t)t * K,
                   w + (int64_t)t * K);
 }
@@ -95,6 +100,72 @@ __global__ void __launch_bounds__(256) router_select_bwd_kernel(const void* scor
       const int e = lane + 64 * v;
       const float dz = round_dt((ex[v] / sum) * (g[v] - inner), dtype);
       if (e < E) store_score(dscores, base + e, dz / sel_param, dtype);
+    }
+    return;
+  }
+  if (mode == CSMOE_SEL_SIGMOID_NORM) {
+    // autograd of smoe_sigmoidgating.py:33-42 / smoeut_norm.py:112-125.  The K keys v are a tensor of the scores' dtype used twice,
+    // as the numerator and in the K-sum, so they receive two gradients, each rounded to that dtype and added in it.  The division's
+    // backward runs in torch's own order (derivatives.yaml, `self / other`): d self = grad / other, d other = -grad * ((self / other)
+    // / other) summed over K.
+    //   bf16 quotient (bf16 scores and `round_sum_bf16`: w, v and the denominator are bf16 tensors): d w arrives rounded, every op of
+    //     the sequence is a bf16 tensor op and the K-sum of d other is rounded once;
+    //   fp32 quotient: the sequence in fp32; under `round_sum_bf16` the denominator is a bf16 tensor and its gradient is rounded.
+    // sigmoid's backward is (d v * (1 - v)) * v in fp32, rounded once (a tensor op of the scores' dtype).  The scores then hold two
+    // gradients of their dtype, the fp32 softmax's (rounded by its input cast) and the sigmoid's, added in that dtype.
+    // The LLaVA bf16 module (`sum` a bf16 tensor op) and the pretrain bf16 stream (`sum` fp32 under autocast, then `.to(bf16)`) are two
+    // graphs with the same bits: the bf16 gradient of the denominator widens and narrows exactly.  Emulated line by line with torch
+    // ops on the CPU this reproduces autograd's d scores bit for bit in the three bf16 cases (tests/test_sigmoid_cpu.py); one rounding
+    // of the closed form dw / den - sum(dw v) / den^2 left about a tenth of the elements different, by up to 3.9e-3 at |d| <= 0.7.
+    const bool bq = round_sum_bf16 && dtype == CSMOE_BF16;
+    int myi = -1;
+    float mydw = 0.f, myv = 0.f;
+    if (lane < K) {
+      myi = idx[(int64_t)t * K + lane];
+      mydw = dw ? dw[(int64_t)t * K + lane] : 0.f;
+      myv = round_dt(sigmoidf_(load_score(scores, base + myi, dtype)), dtype);
+    }
+    float ssum = 0.f;
+    for (int k = 0; k < K; ++k) ssum += __shfl(myv, k, 64);        // slot order, as the forward
+    const float denom = round_sum_bf16 ? (float)(bf16)ssum : ssum;
+    float dv;
+    if (bq) {
+      const float dwr = (float)(bf16)mydw;
+      const float q = (float)(bf16)((float)(bf16)(myv / denom) / denom);
+      const float t1 = lane < K ? (float)(bf16)(-dwr * q) : 0.f;
+      float dd = 0.f;
+      for (int k = 0; k < K; ++k) dd += __shfl(t1, k, 64);
+      dv = (float)(bf16)((float)(bf16)(dwr / denom) + (float)(bf16)dd);
+    } else {
+      const float t1 = lane < K ? -mydw * ((myv / denom) / denom) : 0.f;
+      float dd = 0.f;
+      for (int k = 0; k < K; ++k) dd += __shfl(t1, k, 64);
+      if (round_sum_bf16) dd = (float)(bf16)dd;
+      dv = round_dt(round_dt(mydw / denom, dtype) + round_dt(dd, dtype), dtype);
+    }
+    const float dz = lane < K ? round_dt((dv * (1.f - myv)) * myv, dtype) : 0.f;
+    float g[VPL], p[VPL], direct[VPL];
+    float inner = 0.f;
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+      const int e = lane + 64 * v;
+      p[v] = (softmax && e < E) ? softmax[base + e] : 0.f;
+      g[v] = (dsoftmax && e < E) ? dsoftmax[base + e] : 0.f;
+      direct[v] = 0.f;
+      inner += g[v] * p[v];
+    }
+    inner = wave_sum(inner);
+    for (int k = 0; k < K; ++k) {
+      const int ei = __shfl(myi, k, 64);
+      const float d = __shfl(dz, k, 64);
+#pragma unroll
+      for (int v = 0; v < VPL; ++v)
+        if (lane + 64 * v == ei) direct[v] = d;
+    }
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+      const int e = lane + 64 * v;
+      if (e < E) store_score(dscores, base + e, round_dt(p[v] * (g[v] - inner), dtype) + direct[v], dtype);
     }
     return;
   }

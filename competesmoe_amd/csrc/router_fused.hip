@@ -150,8 +150,14 @@ __global__ void __launch_bounds__(64 * RF_WAVES) gate_select_kernel(const bf16* 
     }
     const int64_t tt = live ? t : 0;
     int myi[4];
-    select_row_g16(s, i16, E, K, mode, round_sum_bf16, sel_param, CSMOE_BF16, live, softmax ? softmax + tt * E : nullptr,
-                   idx + tt * K, w + tt * K, myi);
+    // SEL_SIGMOID_NORM: a routine of its own behind a uniform branch of the run-time instantiation; SPEC folds the test away and
+    // compiles to what it was
+    if (!SPEC && mode == CSMOE_SEL_SIGMOID_NORM)
+      select_row_signorm_g16(s, i16, E, K, round_sum_bf16, CSMOE_BF16, live, softmax ? softmax + tt * E : nullptr, idx + tt * K,
+                             w + tt * K, myi);
+    else
+      select_row_g16(s, i16, E, K, mode, round_sum_bf16, sel_param, CSMOE_BF16, live, softmax ? softmax + tt * E : nullptr,
+                     idx + tt * K, w + tt * K, myi);
     if (block_hist && live) {
       // the ids this lane selected, from its registers: reading them back from `idx` put a store acknowledgement and a global load
       // (~2 us) into each of the four passes of every wave -- the tail in which the E = 64 router lost its 4.9 TB/s

@@ -1,5 +1,5 @@
 // Router selection of ONE token row by one wave (lane l holds scores l, l+64, ...: VPL values per lane, E <= 64*VPL): fp32 softmax,
-// K rounds of wave arg-max with the lowest-index tie break, and the renormalised weights of the six selection modes of
+// K rounds of wave arg-max with the lowest-index tie break, and the renormalised weights of the selection modes of
 // include/csmoe.h.  Shared by router_select_kernel (moe_kernels.hip) and the one-pass router (router_fused.hip), so that the fused
 // path selects and weighs bit-identically.
 // (moe_model/model/moe/moe.py:113-132, smoe.py:44, competesmoe.py:246-255; moe_pretrain_model/layers/moe/deepseekv2.py:140-142,
@@ -153,6 +153,57 @@ __device__ __forceinline__ void select_row_temp(const float (&s)[VPL], int lane,
   float es = wave_sum(ek);
   float wk = ek / es;
   if (tflags & CSMOE_TEMP_W_BF16) wk = (float)(bf16)wk;
+  if (lane < K) { w_row[lane] = wk; idx_row[lane] = myi; }
+}
+
+// CSMOE_SEL_SIGMOID_NORM (MoEUT's sigmoid gate: moe_model/model/moe/smoe_sigmoidgating.py:33-42; moe_pretrain_model/layers/moe/
+// smoeut_norm.py:112-125): key = sigmoid(score) in the scores' dtype; top-K of the keys; den = the fp32 K-sum in slot order, rounded to
+// bf16 under `round_sum_bf16` (`.to(x.dtype)`); w = key / den, NO epsilon and no guard (K zero keys divide by zero as the reference
+// does); the quotient is rounded to bf16 when both operands are bf16 tensors (bf16 scores and `round_sum_bf16`).  sm_row receives the
+// fp32 softmax of the scores.  A routine of its own, as select_row_temp is and for its reason: the older rules' code stays as it was.
+template <int VPL>
+__device__ __forceinline__ void select_row_signorm(const float (&s)[VPL], int lane, int E, int K, int round_sum_bf16, int dtype,
+                                                   float* sm_row, int32_t* idx_row, float* w_row) {
+  float key[VPL];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int v = 0; v < VPL; ++v) mx = fmaxf(mx, s[v]);
+  mx = wave_max(mx);
+  float ex[VPL], sum = 0.f;
+#pragma unroll
+  for (int v = 0; v < VPL; ++v) {
+    int e = lane + 64 * v;
+    ex[v] = e < E ? expf(s[v] - mx) : 0.f;
+    sum += ex[v];
+  }
+  sum = wave_sum(sum);
+#pragma unroll
+  for (int v = 0; v < VPL; ++v) {
+    int e = lane + 64 * v;
+    if (sm_row && e < E) sm_row[e] = ex[v] / sum;
+    key[v] = e < E ? round_dt(sigmoidf_(s[v]), dtype) : -INFINITY;
+  }
+  float vsum = 0.f;
+  float myv = 0.f;
+  int myi = 0;
+  for (int k = 0; k < K; ++k) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+      int e = lane + 64 * v;
+      if (key[v] > bv || (key[v] == bv && e < bi)) { bv = key[v]; bi = e; }
+    }
+    wave_argmax(bv, bi);
+#pragma unroll
+    for (int v = 0; v < VPL; ++v)
+      if (lane + 64 * v == bi) key[v] = -INFINITY;
+    if (lane == k) { myv = bv; myi = bi; }
+    vsum += bv;   // summed in k order, identical in every lane
+  }
+  const float denom = round_sum_bf16 ? (float)(bf16)vsum : vsum;
+  float wk = myv / denom;
+  if (round_sum_bf16 && dtype == CSMOE_BF16) wk = (float)(bf16)wk;
   if (lane < K) { w_row[lane] = wk; idx_row[lane] = myi; }
 }
 
@@ -325,6 +376,49 @@ __device__ __forceinline__ void select_row_temp_g16(const float (&s)[4], int l16
   for (int j = 0; j < 4; ++j) {
     float wk = ek[j] / es;
     if (tflags & CSMOE_TEMP_W_BF16) wk = (float)(bf16)wk;
+    if (live && l16 + 16 * j < K) { w_row[l16 + 16 * j] = wk; idx_row[l16 + 16 * j] = myi[j]; }
+  }
+}
+
+// CSMOE_SEL_SIGMOID_NORM with sixteen lanes per row: the bits of select_row_signorm<1> (the trees of select_row_g16)
+__device__ __forceinline__ void select_row_signorm_g16(const float (&s)[4], int l16, int E, int K, int round_sum_bf16, int dtype,
+                                                       bool live, float* sm_row, int32_t* idx_row, float* w_row, int (&myi)[4]) {
+  float key[4], ex[4];
+  float mx = g16_max(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])));
+#pragma unroll
+  for (int j = 0; j < 4; ++j) ex[j] = (l16 + 16 * j) < E ? expf(s[j] - mx) : 0.f;
+  const float sum = g16_sum64(ex);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int e = l16 + 16 * j;
+    if (live && sm_row && e < E) sm_row[e] = ex[j] / sum;
+    key[j] = e < E ? round_dt(sigmoidf_(s[j]), dtype) : -INFINITY;
+  }
+  float vsum = 0.f;
+  float myv[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) myi[j] = 0;
+  for (int k = 0; k < K; ++k) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int e = l16 + 16 * j;
+      if (key[j] > bv || (key[j] == bv && e < bi)) { bv = key[j]; bi = e; }
+    }
+    g16_argmax(bv, bi);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (l16 + 16 * j == bi) key[j] = -INFINITY;
+      if (l16 + 16 * j == k) { myv[j] = bv; myi[j] = bi; }
+    }
+    vsum += bv;
+  }
+  const float denom = round_sum_bf16 ? (float)(bf16)vsum : vsum;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float wk = myv[j] / denom;
+    if (round_sum_bf16 && dtype == CSMOE_BF16) wk = (float)(bf16)wk;
     if (live && l16 + 16 * j < K) { w_row[l16 + 16 * j] = wk; idx_row[l16 + 16 * j] = myi[j]; }
   }
 }

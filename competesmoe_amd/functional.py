@@ -566,7 +566,13 @@ def _ffn_backward(dout, w, tab: ExpertTable, saved, need_dx: bool, need_dw: bool
     dot_cols = 0
     if scale_after and need_dw and hpre is None:
         dot_cols = ops.rowdot_cols(bins.n, tab.F, tab.Dout, tab.Dout, ld2, tab.F, hact.dtype)
-    dy, dw = ops.combine_bwd(dout.contiguous(), y if (need_dw and not dot_cols) else None, bins, w, want_dw=need_dw and not dot_cols,
+    # no dot table (the generic kernel: rows that are no whole number of 16-byte pieces, e.g. D = 60) with bf16 rows: the same
+    # arithmetic in three steps, as pretrain/cvmm.py's fallback forms it.  <dout, y> from the combine's backward is the same number
+    # with other roundings (y is rounded, the reference's product is): d w_gate of `smoe_sigmoid` at D = 60 was 5.1e-3 off the
+    # reference's order with it (bound 2e-3).
+    three_step = bool(scale_after and need_dw and hpre is None and not dot_cols and hact.dtype == torch.bfloat16)
+    own_dw = need_dw and not dot_cols and not three_step
+    dy, dw = ops.combine_bwd(dout.contiguous(), y if own_dw else None, bins, w, want_dw=own_dw,
                              act_dtype=hact.dtype, round_products=round_dw)
     if dy_extra is not None:                # gradient of the per-slot outputs (MoEFFNModulesSlots), already in binned order
         dy = dy + dy_extra
@@ -581,9 +587,13 @@ def _ffn_backward(dout, w, tab: ExpertTable, saved, need_dx: bool, need_dw: bool
         dot = torch.empty(bins.n, dot_cols, dtype=torch.float32, device=dev) if dot_cols else None
         dh = ops.grouped_gemm(dyu, tab.w2_ptrs, _flip(tab.layout), ld2, tab.F, bins.offsets, E, epilogue=L.EPI_ACTGRAD_ROWSCALE,
                               act=tab.act, aux=hpre if hpre is not None else hact, row_scale=w_rows, row_dot=dot)
-        del dyu
         if dot is not None:
             dw = ops.finish_row_dot(dot)[bins.slot_of.long()].view(T, bins.K)
+        elif three_step:
+            prod = ops.grouped_gemm(dyu, tab.w2_ptrs, _flip(tab.layout), ld2, tab.F, bins.offsets, E)
+            dw = (prod.float() * hact.float()).sum(-1)[bins.slot_of.long()].view(T, bins.K)
+            del prod
+        del dyu
         if dy_extra is not None:
             # the per-slot outputs (MoEFFNPackedSlots: the diversity loss's operands) are UNWEIGHTED rows of the second product, so
             # their gradient goes through W2^T and the activation gradient as it stands -- the reference backpropagates the

@@ -73,6 +73,8 @@ class Route(NamedTuple):
 
 
 class MoeLayer(nn.Module):
+    SEL = L.SEL_SOFTMAX               # selection rule of `_route` / `topk_expert` (include/csmoe.h)
+    WEIGHTS_XDTYPE = False            # the renormalised weights are x.dtype TENSORS upstream (a bf16 module multiplies them as such)
 
     @staticmethod
     def _dense_input(module, args):
@@ -181,7 +183,7 @@ class MoeLayer(nn.Module):
         the division (denominator rounded to the activation dtype first, as `.to(x.dtype)` does)."""
         K = num_selected or self.num_selected
         shp = gate_logits.shape
-        sm, idx, w = RouterSelect.apply(gate_logits.reshape(-1, shp[-1]), K, L.SEL_SOFTMAX,
+        sm, idx, w = RouterSelect.apply(gate_logits.reshape(-1, shp[-1]), K, self.SEL,
                                         gate_logits.dtype == torch.bfloat16)
         return w.view(*shp[:-1], K), idx.view(*shp[:-1], K), sm.view(shp)
 
@@ -193,7 +195,7 @@ class MoeLayer(nn.Module):
         K, E = self.num_selected, self.gate.weight.shape[0]
         if getattr(self, "_pre_logits", None) is None and ops.gate_select_ok(x2, self.gate.weight, K):
             # one launch that reads x once: logits, softmax, top-K and the binning histogram (csmoe_gate_select)
-            logits, sm, idx, w = GateSelect.apply(x2, self.gate.weight, K, L.SEL_SOFTMAX, x.dtype == torch.bfloat16)
+            logits, sm, idx, w = GateSelect.apply(x2, self.gate.weight, K, self.SEL, x.dtype == torch.bfloat16)
             return Route(logits.view(B, N, E), sm.view(B, N, E), idx.view(B, N, K), w.view(B, N, K))
         logits = self.gate_logits(x)
         w, idx, sm = self.topk_expert(gate_logits=logits)
@@ -206,14 +208,15 @@ class MoeLayer(nn.Module):
         B, N, D = x.shape
         K, E = self.num_selected, self.gate.weight.shape[0]
         x2 = x.reshape(B * N, D)
+        rounded = self.WEIGHTS_XDTYPE and x.dtype == torch.bfloat16     # bf16 weights: the combine rounds w * y before the add
         if (os.environ.get("CSMOE_FUSED_STEP", "1") != "0" and getattr(self, "_pre_logits", None) is None
                 and getattr(self, "_residual", None) is None and E == len(self.experts) and ops.gate_select_ok(x2, self.gate.weight, K)):
             tab, params = self._expert_table(E, x.dtype, x.device)
-            out, logits, sm, idx, w = SparseMoEModules.apply(x2, self.gate.weight, K, L.SEL_SOFTMAX, x.dtype == torch.bfloat16, tab,
-                                                             L.COMBINE_SEQ, *params)
+            out, logits, sm, idx, w = SparseMoEModules.apply(x2, self.gate.weight, K, self.SEL, x.dtype == torch.bfloat16, tab,
+                                                             L.COMBINE_SEQ_RW if rounded else L.COMBINE_SEQ, *params)
             return Route(logits.view(B, N, E), sm.view(B, N, E), idx.view(B, N, K), w.view(B, N, K)), out.view(B, N, out.shape[-1])
         route = self._route(x)
-        return route, self.compute_moe(route.idx, route.w, None, x)
+        return route, self.compute_moe(route.idx, route.w, None, x, weights_rounded=rounded)
 
     def _router_aux(self, route: "Route", wanted: bool, like: torch.Tensor, keep_metrics: bool = False):
         """(auxiliary loss, infor_aux) of a sparse step: balance + z-loss when `wanted` (smoe.py:51-62), else a zero and {}.

@@ -42,6 +42,14 @@ enum {
   CSMOE_SEL_TEMP_SOFTMAX_TOPK = 5 /* p = softmax(fp32) of (score / sel_param rounded to the scores' dtype) -> topk(p) -> softmax over
                                 the K values; the `softmax` output holds p.  `round_sum_bf16` is a set of CSMOE_TEMP_* flags here
                                 (XMoE: moe_model/model/moe/xmoe.py:90-91, 48-51; moe_pretrain_model/layers/moe/xmoe.py:161-162) */
+  ,
+  CSMOE_SEL_SIGMOID_NORM = 6 /* topk(sigmoid in the scores' dtype) -> w / den, den = the fp32 K-sum in slot order, rounded to bf16
+                                under `round_sum_bf16` (`.to(x.dtype)`).  No epsilon and no guard: a row whose K keys are all zero
+                                divides by zero exactly as the reference does (NaN weights).  The quotient is fp32, except that bf16
+                                scores WITH `round_sum_bf16` make both operands bf16 tensors and the quotient a bf16 tensor op: w then
+                                holds bf16 values (the array stays fp32).  `softmax` is the fp32 softmax of the scores.
+                                (MoEUT's sigmoid gate: moe_model/model/moe/smoe_sigmoidgating.py:33-42;
+                                moe_pretrain_model/layers/moe/smoeut_norm.py:112-125) */
 };
 /* Rounding points of the cosine router (flags; the first two are SEL_TEMP_SOFTMAX_TOPK's `round_sum_bf16`). */
 enum {
@@ -124,7 +132,9 @@ int csmoe_gate_logits(const void* x, const void* w_gate, void* logits, int T, in
 /* scores[T,E] (dtype) -> softmax[T,E] fp32 (of the scores), idx[T,K] int32 (descending value, ties ->
  * lowest index), w[T,K] fp32.  `round_sum_bf16` != 0 rounds the K-sum to bf16 before the division
  * (`.to(x.dtype)` on the denominator, smoe.py:44).  softmax may be null for SEL_TOPK_SOFTMAX/SIGMOID.
- * `sel_param`: the scale of SEL_TOPK_SIGMOID (args.scale_weight), ignored by the other rules.
+ * `sel_param`: the scale of SEL_TOPK_SIGMOID (args.scale_weight), the temperature of SEL_TEMP_SOFTMAX_TOPK, ignored by the other
+ * rules.  SEL_SIGMOID_NORM as the reference reaches it: fp32 scores, round_sum_bf16 = 0 (fp32 modules); bf16 scores, 1 (a bf16
+ * module, a bf16 stream: bf16 quotient); bf16 scores, 0 (bf16 autocast on an fp32 stream: `sum` is fp32-policy, fp32 quotient).
  * replaces topk_expert + renorm (moe_model/model/moe/moe.py:113-132; smoe.py:19-44;
  * competesmoe.py:246-255; pretrain smoe.py:123-143, deepseekv2.py:140-142, deepseekv3.py:147-151). */
 int csmoe_router_select(const void* scores, int dtype, int T, int E, int K, int sel_mode, int round_sum_bf16,
@@ -157,6 +167,7 @@ int csmoe_bin_tokens_hist(const int32_t* idx, int n, int E, int chunk, const int
  *   gives them on those logits (identical bits: same selection routine);  block_hist (nullable): [ceil(T / rows)][E] counts of
  *   the ids of each block of csmoe_gate_select_rows() token rows, i.e. chunk = rows*K for csmoe_bin_tokens_hist.
  * Shapes it takes: csmoe_gate_select_ok(...) = 1 (bf16, E <= 64, D % 8 == 0); others use the two separate entries.
+ * Rules it takes: SEL_SOFTMAX .. SEL_TOPK_SIGMOID and SEL_SIGMOID_NORM (SEL_TEMP_SOFTMAX_TOPK is csmoe_cosine_select's).
  * replaces `self.gate(x)` + `topk_expert` (moe_model/model/moe/smoe.py:42-44, moe.py:113-132) and `F.linear(x, w_gate)` + top-k
  * (moe_pretrain_model/layers/moe/moe.py:121, smoe.py:30-40, deepseekv2.py:140-142). */
 int csmoe_gate_select_ok(int T, int D, int E, int K, int dtype);

@@ -2,8 +2,9 @@
 """One-pass router (csmoe_gate_select) against gate GEMM + router_select + counting pass at the headline token count, and the
 one-pass XMoE cosine router (csmoe_cosine_select) against the torch-op form of the same gate and against csmoe_gate_select at the
 same T and D (it streams the same bytes); `perturbed`: the same kernel in its CSMOE_COS_NORM_THETA mode (`smoe_perturbed`) against
-the XMoE mode of the same build and the torch-op gate.
-usage (GPU box): python tools/router_bench.py [linear|cosine|perturbed|all] [rounds [iters]]   (rounds / iters: the cosine cases)
+the XMoE mode of the same build and the torch-op gate; `sigmoid`: csmoe_gate_select with the rule CSMOE_SEL_SIGMOID_NORM
+(`smoe_sigmoidgating` / `smoe_sigmoid`) beside its softmax rule at the same shape, in the run-time and the specialised instantiation.
+usage (GPU box): python tools/router_bench.py [linear|cosine|perturbed|sigmoid|all] [rounds [iters]]   (rounds / iters: not `linear`)
 
 What the event times are: every candidate is called through its Python entry, which allocates its outputs (five to seven
 torch.empty) and launches; the torch-op gate is about a dozen eager launches per call.  The figures are therefore the cost of a
@@ -108,13 +109,50 @@ def perturbed(rounds=3, iters=500):
         print(f"T={T} D={D} E={E} K={K} {k}: " + " / ".join(f"{t:.1f}" for t in v) + f" us{rate}", flush=True)
 
 
+def sigmoid(rounds=3, iters=500):
+    """The shape and the method of `cosine`.  csmoe_gate_select with SEL_SIGMOID_NORM, `round_sum_bf16` 1 (a bf16 module: bf16
+    quotient) and 0 (bf16 autocast on an fp32 stream), beside SEL_SOFTMAX in the same run-time instantiation (`round_sum_bf16` 0 keeps
+    K = 2 out of the specialised kernel) and in the specialised one: all four read the same bytes.  The spread between the rounds of
+    the run-time softmax line is the yardstick for the two sigmoid lines.  Then the selection backward of both rules."""
+    dev = "cuda"
+    T, D, E, K = 32768, 4096, 64, 2
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn(T, D, device=dev, generator=g).to(torch.bfloat16)
+    wg = (torch.randn(E, D, device=dev, generator=g) * D ** -0.5).to(torch.bfloat16)
+    dw, dsm = torch.randn(T, K, device=dev, generator=g), torch.randn(T, E, device=dev, generator=g)
+    saved = {m: ops.gate_select(x, wg, K, m, True) for m in (L.SEL_SIGMOID_NORM, L.SEL_SOFTMAX)}
+
+    def bwd(m):
+        lg, sm, idx, w = saved[m]
+        return lambda: ops.router_select_bwd(lg, K, m, True, sm, idx, w, dw, dsm)
+    cands = {
+        "gate_select SEL_SIGMOID_NORM round_sum_bf16=1 (run-time instantiation)": lambda: ops.gate_select(x, wg, K, L.SEL_SIGMOID_NORM, True),
+        "gate_select SEL_SIGMOID_NORM round_sum_bf16=0 (run-time instantiation)": lambda: ops.gate_select(x, wg, K, L.SEL_SIGMOID_NORM, False),
+        "gate_select SEL_SOFTMAX round_sum_bf16=0 (run-time instantiation)": lambda: ops.gate_select(x, wg, K, L.SEL_SOFTMAX, False),
+        "gate_select SEL_SOFTMAX round_sum_bf16=1 (specialised kernel)": lambda: ops.gate_select(x, wg, K, L.SEL_SOFTMAX, True),
+        "router_select_bwd SEL_SIGMOID_NORM": bwd(L.SEL_SIGMOID_NORM),
+        "router_select_bwd SEL_SOFTMAX": bwd(L.SEL_SOFTMAX),
+    }
+    gb = T * D * 2 / 1e9
+    times = {k: [] for k in cands}
+    with torch.no_grad():
+        for _ in range(rounds):
+            for k, fn in cands.items():
+                times[k].append(timed(fn, iters))
+    for k, v in times.items():
+        rate = f" ({gb / min(v) * 1e6:.0f} GB/s of x at the best round)" if "bwd" not in k else ""
+        print(f"T={T} D={D} E={E} K={K} {k}: " + " / ".join(f"{t:.1f}" for t in v) + f" us{rate}", flush=True)
+
+
 def main():
     which = sys.argv[1] if len(sys.argv) > 1 else "all"
     if which in ("cosine", "all"):
         cosine(*(int(a) for a in sys.argv[2:4]))
     if which in ("perturbed", "all"):
         perturbed(*(int(a) for a in sys.argv[2:4]))
-    if which in ("cosine", "perturbed"):
+    if which in ("sigmoid", "all"):
+        sigmoid(*(int(a) for a in sys.argv[2:4]))
+    if which in ("cosine", "perturbed", "sigmoid"):
         return
     dev = "cuda"
     for T, D, E, K in ((32768, 4096, 64, 2), (32768, 4096, 64, 8), (32768, 1024, 64, 2), (32768, 4096, 16, 2), (12800, 1152, 4, 2)):
