@@ -5,4 +5,12 @@ Importing this package loads `lib/libcsmoe_hip.so`; there is no CPU fallback.
 """
 from . import _lib  # noqa: F401  (fails loudly when the HIP library is not built)
 
-__all__ = ["_lib"]
+__all__ = ["_lib", "decode_rows"]
+
+
+def decode_rows(n=None) -> int:
+    """Decode-path switch: `n` = the largest number of routed rows (T * K) a forward-only call may have to run its expert GEMMs on
+    the weight-streaming kernel (csmoe_grouped_gemm_skinny) without a dispatch copy; 0 (the default, or CSMOE_DECODE_ROWS unset)
+    switches the path off.  Returns the value in force; `decode_rows()` only reads it."""
+    from . import ops
+    return ops.decode_rows(n)

@@ -62,6 +62,8 @@ SIGNATURES = {
     "csmoe_combine": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "csmoe_combine_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "csmoe_grouped_gemm": (_i, [_p, _l, _p, _i, _l, _p, _p, _i, _i, _i, _i, _p, _p, _p, _l, _i, _i, _i, _i, _p]),
+    "csmoe_grouped_gemm_skinny": (_i, [_p, _l, _p, _i, _p, _i, _l, _p, _p, _i, _i, _i, _i, _p, _p, _l, _i, _i, _i, _p]),
+    "csmoe_grouped_gemm_skinny_ok": (_i, [_i, _i, _i, _l, _l, _l, _i, _i, _i]),
     "csmoe_dense_gemm": (_i, [_p, _l, _p, _i, _l, _p, _i, _i, _i, _p, _p, _p, _l, _i, _i, _i, _i, _p]),
     "csmoe_grouped_wgrad": (_i, [_p, _l, _p, _l, _p, _i, _i, _i, _i, _p, _l, _i, _i, _i, _i, _p, _p]),
     "csmoe_expert_order": (_i, [_p, _i, _p, _p]),

@@ -39,6 +39,10 @@ int gg8c_rowspace(const void* A, int64_t lda, const void* const* b_ptrs, int64_t
 int gg8_rowspace_rest(const void* A, int64_t lda, const void* const* b_ptrs, int b_layout, int64_t ldb,
                       const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2,
                       const void* aux, int64_t ldc, int epilogue, int act, hipStream_t st);
+bool gg_skinny_shape_ok(int64_t lda, int64_t ldb, int64_t ldc, int M, int N, int Kd);
+int gg_skinny_rowspace(const void* A, int64_t lda, const int32_t* src_rows, int src_div, const void* const* b_ptrs, int b_layout,
+                       int64_t ldb, const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C,
+                       void* C2, int64_t ldc, int epilogue, int act, hipStream_t st);
 int k_quantize_mxfp8(const void* const* x_ptrs, const void* x_single, int E, int64_t ldx, int R, int C, int in_dtype, int transpose,
                      void* q, void* s, hipStream_t st);
 int k_quantize_mxfp8_both(const void* const* x_ptrs, const void* x_single, int E, int64_t ldx, int R, int C, int in_dtype, void* q,
@@ -372,6 +376,51 @@ int csmoe_combine_bwd(const void* dout, const void* y, const int32_t* perm, cons
   CSMOE_CHECK_ARG(dtype_ok(dtype) && K > 0 && T >= 0 && D > 0, "combine_bwd: bad arguments");
   CSMOE_CHECK_ARG(T == 0 || (dout && slot_of && dy), "combine_bwd: null pointer");
   return k_combine_bwd(dout, y, slot_of, w, dy, dw, T, K, D, dtype, round_products, (hipStream_t)stream);
+}
+
+// ---- few-row (decode) grouped GEMM: gemm_skinny.hip.  Refusals (CSMOE_ERR_UNSUPPORTED) come before any pointer is looked at and
+// before anything is launched, so nothing is ever half-written.
+static bool skinny_epilogue_ok(int epilogue) {
+  return epilogue == CSMOE_EPI_PLAIN || epilogue == CSMOE_EPI_BIAS || epilogue == CSMOE_EPI_BIAS_ACT ||
+         epilogue == CSMOE_EPI_ROUND_BIAS32_ACT;
+}
+
+int csmoe_grouped_gemm_skinny_ok(int M, int N, int Kd, int64_t lda, int64_t ldb, int64_t ldc, int b_layout, int epilogue, int dtype) {
+  if (dtype != CSMOE_BF16 || !skinny_epilogue_ok(epilogue)) return 0;
+  if (b_layout != CSMOE_B_NK && b_layout != CSMOE_B_KN) return 0;
+  if (M < 0 || N <= 0 || Kd <= 0 || lda < Kd || ldc < N || ldb < (b_layout == CSMOE_B_NK ? Kd : N)) return 0;
+  return gg_skinny_shape_ok(lda, ldb, ldc, M, N, Kd) ? 1 : 0;
+}
+
+int csmoe_grouped_gemm_skinny(const void* A, int64_t lda, const int32_t* src_rows, int src_div, const void* const* b_ptrs,
+                              int b_layout, int64_t ldb, const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N,
+                              int Kd, void* C, void* C2, int64_t ldc, int epilogue, int act, int dtype, csmoe_stream_t stream) {
+  CSMOE_CHECK_ARG(dtype_ok(dtype), "grouped_gemm_skinny: bad dtype %d", dtype);
+  CSMOE_CHECK_ARG(b_layout == CSMOE_B_NK || b_layout == CSMOE_B_KN, "grouped_gemm_skinny: bad B layout %d", b_layout);
+  CSMOE_CHECK_ARG(epilogue >= 0 && epilogue <= CSMOE_EPI_ACCUM && act >= 0 && act <= 5, "grouped_gemm_skinny: bad epilogue/act");
+  CSMOE_CHECK_ARG(!src_rows || src_div > 0, "grouped_gemm_skinny: src_div = %d must be positive", src_div);
+  if (epilogue == CSMOE_EPI_ACCUM) return accum_unsupported("grouped_gemm_skinny");
+  if (dtype != CSMOE_BF16) {
+    csmoe_set_error("grouped_gemm_skinny: bf16 only (fp32 rows take csmoe_grouped_gemm)");
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  if (!skinny_epilogue_ok(epilogue)) {
+    csmoe_set_error("grouped_gemm_skinny: forward epilogues only (PLAIN, BIAS, BIAS_ACT, ROUND_BIAS32_ACT), got %d", epilogue);
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  CSMOE_CHECK_ARG(E > 0 && M >= 0 && N > 0 && Kd > 0, "grouped_gemm_skinny: bad shape E=%d M=%d N=%d Kd=%d", E, M, N, Kd);
+  CSMOE_CHECK_ARG(lda >= Kd && ldc >= N && ldb >= (b_layout == CSMOE_B_NK ? Kd : N), "grouped_gemm_skinny: leading dimension too small");
+  CSMOE_CHECK_ARG(b_ptrs && offsets, "grouped_gemm_skinny: null pointer table / offsets");
+  if (M == 0) return CSMOE_OK;
+  const bool has_c2 = epilogue == CSMOE_EPI_BIAS_ACT || epilogue == CSMOE_EPI_ROUND_BIAS32_ACT;
+  CSMOE_CHECK_ARG(A && (C || (has_c2 && C2)), "grouped_gemm_skinny: null pointer");
+  if (!gg_skinny_shape_ok(lda, ldb, ldc, M, N, Kd) || ((uintptr_t)A & 15) || ((uintptr_t)C & 15) || ((uintptr_t)C2 & 15)) {
+    csmoe_set_error("grouped_gemm_skinny: needs N, Kd, lda, ldb, ldc multiples of 8, 16-byte aligned operands and panels under "
+                    "2 GiB (csmoe_grouped_gemm_skinny_ok); M=%d N=%d Kd=%d", M, N, Kd);
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  return gg_skinny_rowspace(A, lda, src_rows, src_div, b_ptrs, b_layout, ldb, bias_ptrs, offsets, E, M, N, Kd, C, C2, ldc, epilogue,
+                            act, (hipStream_t)stream);
 }
 
 int csmoe_grouped_gemm(const void* A, int64_t lda, const void* const* b_ptrs, int b_layout, int64_t ldb,

@@ -6,6 +6,7 @@ Reference parity notes are on each class (file:line of the reference code whose 
 from __future__ import annotations
 
 import os
+import threading
 import weakref
 from dataclasses import dataclass
 from typing import List, Optional
@@ -464,12 +465,63 @@ def _side_stream(dev) -> "torch.cuda.Stream":
     return st
 
 
-def _ffn_forward(x2, w, idx, tab: ExpertTable, combine_mode: int, obias, residual=None, before_gemm2=None, masters=None):
+# ---- does this call need a backward?  Decided like the autograd engine decides whether to record the node: grad mode was on when
+# `apply` was called AND some input requires grad.  Inside Function.forward grad mode is always off and ctx.needs_input_grad
+# lists the inputs that require grad whatever the mode was (a model under torch.no_grad() still has parameters that do), so the
+# functions below note the mode on their way into `apply`.
+_APPLY_MODE = threading.local()
+
+
+class _ForwardAware(torch.autograd.Function):
+    @classmethod
+    def apply(cls, *args, **kwargs):
+        stack = _APPLY_MODE.__dict__.setdefault("stack", [])
+        stack.append(torch.is_grad_enabled())
+        try:
+            return super().apply(*args, **kwargs)
+        finally:
+            stack.pop()
+
+
+def _needs_backward(ctx) -> bool:
+    stack = getattr(_APPLY_MODE, "stack", None)
+    grad_mode = stack[-1] if stack else True          # forward called some other way: assume a backward may follow
+    return bool(grad_mode and any(ctx.needs_input_grad))
+
+
+def _decode_gemms_ok(tab: ExpertTable, n: int, dtype) -> bool:
+    """Both expert GEMMs of a call with n routed rows fit csmoe_grouped_gemm_skinny (bf16, the 8-element shape rule)."""
+    ld1 = tab.D if tab.layout == L.B_NK else tab.F
+    ld2 = tab.F if tab.layout == L.B_NK else tab.Dout
+    epi2 = L.EPI_BIAS if tab.b2_ptrs is not None else L.EPI_PLAIN
+    return (ops.grouped_gemm_skinny_ok(n, tab.F, tab.D, tab.D, ld1, tab.F, tab.layout, tab.epi1, dtype)
+            and ops.grouped_gemm_skinny_ok(n, tab.Dout, tab.F, tab.F, ld2, tab.Dout, tab.layout, epi2, dtype))
+
+
+def _ffn_forward(x2, w, idx, tab: ExpertTable, combine_mode: int, obias, residual=None, before_gemm2=None, masters=None,
+                 need_backward: bool = True):
     """`before_gemm2`: a stream the launch stream must wait for before the second grouped GEMM (operand cast running beside GEMM 1).
     `masters` = (keys fp32, k_copy bf16, values fp32, v_copy bf16): the forward GEMMs read the fp32 masters and convert inside
-    their tile fill (csmoe_grouped_gemm_f32w), writing the bf16 copies the backward GEMMs read through `tab`'s pointer tables."""
+    their tile fill (csmoe_grouped_gemm_f32w), writing the bf16 copies the backward GEMMs read through `tab`'s pointer tables.
+    `need_backward`: False when the calling autograd function's node is not recorded (_needs_backward: grad mode off at `apply`, or
+    no input that requires grad).  Such a call with at most ops.decode_rows()
+    routed rows takes the decode path: no dispatch copy (the first GEMM gathers from x2 through bins.perm), both GEMMs on the
+    weight-streaming kernel, no pre-activation written; `saved` keeps its shape with xs = hpre = None."""
     T = x2.shape[0]
     bins = ops.bin_tokens(idx, tab.E)
+    if (not need_backward and masters is None and 0 < bins.n <= ops.decode_rows() and x2.dtype == torch.bfloat16
+            and x2.data_ptr() % 16 == 0 and _decode_gemms_ok(tab, bins.n, x2.dtype)):
+        ld1 = tab.D if tab.layout == L.B_NK else tab.F
+        ld2 = tab.F if tab.layout == L.B_NK else tab.Dout
+        _, hact = ops.grouped_gemm_skinny(x2, tab.w1_ptrs, tab.layout, ld1, tab.F, bins.offsets, tab.E, bias_ptrs=tab.b1_ptrs,
+                                          epilogue=tab.epi1, act=tab.act, want_c2=True, want_c=False, src_rows=bins.perm,
+                                          src_div=bins.K)
+        if before_gemm2 is not None:
+            torch.cuda.current_stream().wait_stream(before_gemm2)
+        y = ops.grouped_gemm_skinny(hact, tab.w2_ptrs, tab.layout, ld2, tab.Dout, bins.offsets, tab.E, bias_ptrs=tab.b2_ptrs,
+                                    epilogue=L.EPI_BIAS if tab.b2_ptrs is not None else L.EPI_PLAIN)
+        out = ops.combine(y, bins, idx, w, combine_mode, T, obias=obias, residual=residual)
+        return out, (bins, None, None, hact, y, combine_mode, idx)
     xs = ops.dispatch_tokens(x2, bins)
     if masters is not None:
         keys, k_copy, values, v_copy = masters
@@ -642,7 +694,7 @@ def _ffn_backward(dout, w, tab: ExpertTable, saved, need_dx: bool, need_dw: bool
     return dx2, dw, grads
 
 
-class MoEFFNModules(torch.autograd.Function):
+class MoEFFNModules(_ForwardAware):
     """dispatch -> grouped GEMM(+bias, act) -> grouped GEMM(+bias) -> combine for experts held as SEPARATE nn.Module
     parameters (LLaVA stack).  Replaces MoeLayer.compute_moe (moe_model/model/moe/moe.py:172-213) and its autograd.
 
@@ -652,7 +704,7 @@ class MoEFFNModules(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x2, w, idx, tab: ExpertTable, combine_mode: int, *params):
         x2 = x2.contiguous()
-        out, saved = _ffn_forward(x2, w, idx, tab, combine_mode, None)
+        out, saved = _ffn_forward(x2, w, idx, tab, combine_mode, None, need_backward=_needs_backward(ctx))
         ctx.tab, ctx.saved, ctx.w = tab, saved, w
         ctx.n_params = len(params)
         ctx.handoff = _take_handoff()
@@ -676,7 +728,7 @@ class MoEFFNModules(torch.autograd.Function):
         return (dx2, dw, None, None, None, *pg)
 
 
-class SparseMoEModules(torch.autograd.Function):
+class SparseMoEModules(_ForwardAware):
     """GateSelect + MoEFFNModules as ONE node -- router_policy / topk_expert + compute_moe of a sparse step (moe_model/model/moe/
     smoe.py:39-64, moe.py:113-213) -- so that the two gradient streams of x, through the gate and through the experts, meet inside
     the gather-sum of the binned rows (`csmoe_dispatch_rows_bwd(..., add)`: round(round(sum_k dxs) + dx_gate), the bits of autograd's
@@ -692,7 +744,7 @@ class SparseMoEModules(torch.autograd.Function):
         if wg.dtype != x2.dtype:
             wg = wg.to(x2.dtype)
         logits, sm, idx, w = ops.gate_select(x2, wg, K, mode, round_sum_bf16, want_softmax=True)
-        out, saved = _ffn_forward(x2, w, idx, tab, combine_mode, None)
+        out, saved = _ffn_forward(x2, w, idx, tab, combine_mode, None, need_backward=_needs_backward(ctx))
         ctx.save_for_backward(x2, wg, logits, sm, idx, w)
         ctx.cfg = (K, mode, round_sum_bf16)
         ctx.w_dtype = w_gate.dtype
@@ -755,7 +807,7 @@ class _SlotMap:
         self.perm, self.K, self.n = index, 1, n
 
 
-class MoEFFNModulesSlots(torch.autograd.Function):
+class MoEFFNModulesSlots(_ForwardAware):
     """MoEFFNModules that also returns the expert outputs per (token, k) slot, y_tk [T, K, Dout] -- what
     `torch.gather(expert_outputs, 2, idx)` takes out of the dense competition pass for the diversity loss
     (moe_model/model/moe/competesmoe.py:256-258), from the sparse step's own rows (same bits), so that the dense pass need not keep
@@ -764,7 +816,7 @@ class MoEFFNModulesSlots(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x2, w, idx, tab: ExpertTable, combine_mode: int, *params):
         x2 = x2.contiguous()
-        out, saved = _ffn_forward(x2, w, idx, tab, combine_mode, None)
+        out, saved = _ffn_forward(x2, w, idx, tab, combine_mode, None, need_backward=_needs_backward(ctx))
         bins, y = saved[0], saved[4]
         y_tk = ops.dispatch_rows(y, _SlotMap(bins.slot_of, bins.n))           # y_tk[t*K+k] = y[slot_of[t*K+k]]
         ctx.tab, ctx.saved, ctx.w = tab, saved, w
@@ -795,7 +847,7 @@ class MoEFFNModulesSlots(torch.autograd.Function):
         return (dx2, dw, None, None, None, *pg)
 
 
-class MoEFFNModulesResidual(torch.autograd.Function):
+class MoEFFNModulesResidual(_ForwardAware):
     """MoEFFNModules with the block's residual added in the combine epilogue: out = round(moe_out + residual)
     (`hidden_states = residual + results`, moe_model/model/multimodal_encoder/siglip_smoe.py:155).  The gradient of the
     residual input is dout itself."""
@@ -803,7 +855,8 @@ class MoEFFNModulesResidual(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x2, residual, w, idx, tab: ExpertTable, combine_mode: int, *params):
         x2 = x2.contiguous()
-        out, saved = _ffn_forward(x2, w, idx, tab, combine_mode, None, residual=residual.contiguous())
+        out, saved = _ffn_forward(x2, w, idx, tab, combine_mode, None, residual=residual.contiguous(),
+                                  need_backward=_needs_backward(ctx))
         ctx.tab, ctx.saved, ctx.w = tab, saved, w
         ctx.n_params = len(params)
         return out
@@ -824,7 +877,7 @@ class MoEFFNModulesResidual(torch.autograd.Function):
         return (dx2, dout if ctx.needs_input_grad[1] else None, dw, None, None, None, *pg)
 
 
-class MoEFFNPacked(torch.autograd.Function):
+class MoEFFNPacked(_ForwardAware):
     """Same pipeline for PACKED expert weights keys[E,D,F], values[E,F,Dout] (pretrain stack): the two `cvmm` calls of
     MoE.compute_scores / the reduction-weight cvmm (moe_pretrain_model/layers/moe/moe.py:397-435, smoe.py:240-248) and
     CVMM.backward (layers/cvmm.py:490-551).  keys/values may be fp32 masters while x is bf16 (autocast): operands are
@@ -903,7 +956,10 @@ class MoEFFNPacked(torch.autograd.Function):
                           w1_ptrs=ops.ptr_table(k_op, E, D * F * es), w2_ptrs=ops.ptr_table(v_op, E, F * Dout * es),
                           b1_ptrs=b1, b2_ptrs=None, param_dtype=keys.dtype, epi1=epi1, scale_after_gemm=combine_mode == L.COMBINE_DOT)
         out, saved = _ffn_forward(x2, w, idx, tab, combine_mode, ob, residual=None if residual is None else residual.contiguous(),
-                                  before_gemm2=side, masters=masters)
+                                  before_gemm2=side, masters=masters,
+                                  # the decode path reads bf16 operands that exist already: bf16 parameters, or the operand cache's
+                                  # copies; a call that had to cast fp32 masters first has paid more than the path saves
+                                  need_backward=_needs_backward(ctx) or not ((keys.dtype == op or k_hit) and (values.dtype == op or v_hit)))
         ctx.has_residual = residual is not None
         if stats is not None:               # the activated scores, for the caller's `relu_pass_rate` log (moe.py:406-414)
             stats["hact"] = saved[3]
@@ -937,7 +993,7 @@ class MoEFFNPacked(torch.autograd.Function):
         return dx2, dw, None, gk, gv, gb, gob, None, None, (dout if (ctx.has_residual and ctx.needs_input_grad[9]) else None), None
 
 
-class MoEFFNPackedSlots(torch.autograd.Function):
+class MoEFFNPackedSlots(_ForwardAware):
     """MoEFFNPacked that also returns the expert outputs per (token, k) slot, [T, K, Dout]: the `topk` outputs the pretrain
     competition step takes out of its dense pass for the diversity loss (moe_pretrain_model/layers/moe/competesmoe.py:403-410), from
     the sparse step's own rows -- so that the dense pass need not keep its outputs (CompetitionAffinityPacked)."""
@@ -964,11 +1020,21 @@ class MoEFFNPackedSlots(torch.autograd.Function):
 
 
 # ======================================================================================================== dense FFN
-def dense_ffn_forward(x2, w1, b1, w2, b2, act: int, layout: int):
+def _dense_skinny(a, wt, layout: int, bias, epilogue: int, act: int, want_c: bool, want_c2: bool):
+    """One dense expert's GEMM on the weight-streaming kernel: E = 1, offsets = [0, M]."""
+    N = wt.shape[0] if layout == L.B_NK else wt.shape[1]
+    return ops.grouped_gemm_skinny(a, ops.ptr_table(wt, 1, 0), layout, wt.stride(0), N, ops.dense_offsets(a.shape[0], a.device), 1,
+                                   bias_ptrs=None if bias is None else ops.ptr_table(bias, 1, 0), epilogue=epilogue, act=act,
+                                   want_c=want_c, want_c2=want_c2)
+
+
+def dense_ffn_forward(x2, w1, b1, w2, b2, act: int, layout: int, need_backward: bool = True):
     """The body of DenseFFN.forward: (y, tensors its backward needs, cfg).  Also called by the expert-parallel functions (ep.py), which
-    run the shared expert between their sends and their first wait."""
+    run the shared expert between their sends and their first wait.  `need_backward` = False (no input takes a gradient) lets a call
+    with at most ops.decode_rows() rows and bf16 operands that exist already run on the weight-streaming kernel (see _ffn_forward)."""
     x2 = x2.contiguous()
     op = x2.dtype
+    casts = [False]
 
     def cast(t):
         if t is None:
@@ -978,9 +1044,11 @@ def dense_ffn_forward(x2, w1, b1, w2, b2, act: int, layout: int):
         if _WEIGHT_CACHE_ON and t._base is None:      # fresh slices (keys[e]) die with the call: their entries could never hit
             c, hit = _cached_copy(t, op)
             if not hit:
+                casts[0] = True
                 c = t.to(op)
                 _remember(t, op, c)
             return c
+        casts[0] = True
         return t.to(op)
 
     epi1 = L.EPI_BIAS_ACT
@@ -990,9 +1058,20 @@ def dense_ffn_forward(x2, w1, b1, w2, b2, act: int, layout: int):
         epi1 = L.EPI_ROUND_BIAS32_ACT
     else:
         w1o, b1o, w2o, b2o = cast(w1), cast(b1), cast(w2), cast(b2)
-    hpre, hact = ops.dense_gemm(x2, w1o, layout, bias=b1o, epilogue=epi1, act=act, want_c2=True, want_c=act != L.ACT_RELU)
-    y = ops.dense_gemm(hact, w2o, layout, bias=b2o, epilogue=L.EPI_BIAS if b2o is not None else L.EPI_PLAIN)
     cfg = (act, layout, w1.dtype, None if b1 is None else b1.dtype, w2.dtype, None if b2 is None else b2.dtype)
+    M, D = x2.shape
+    epi2 = L.EPI_BIAS if b2o is not None else L.EPI_PLAIN
+    if (not need_backward and not casts[0] and 0 < M <= ops.decode_rows() and op == torch.bfloat16 and w1o.dim() == 2 and w2o.dim() == 2
+            and all(t is None or t.data_ptr() % 16 == 0 for t in (x2, w1o, w2o, b1o, b2o))):
+        F_ = w1o.shape[0] if layout == L.B_NK else w1o.shape[1]
+        Dout = w2o.shape[0] if layout == L.B_NK else w2o.shape[1]
+        if (ops.grouped_gemm_skinny_ok(M, F_, D, D, w1o.stride(0), F_, layout, epi1, op)
+                and ops.grouped_gemm_skinny_ok(M, Dout, F_, F_, w2o.stride(0), Dout, layout, epi2, op)):
+            _, hact = _dense_skinny(x2, w1o, layout, b1o, epi1, act, False, True)
+            y = _dense_skinny(hact, w2o, layout, b2o, epi2, L.ACT_NONE, True, False)
+            return y, (x2, w1o, w2o, None, hact), cfg
+    hpre, hact = ops.dense_gemm(x2, w1o, layout, bias=b1o, epilogue=epi1, act=act, want_c2=True, want_c=act != L.ACT_RELU)
+    y = ops.dense_gemm(hact, w2o, layout, bias=b2o, epilogue=epi2)
     return y, (x2, w1o, w2o, hpre, hact), cfg
 
 
@@ -1016,14 +1095,16 @@ def dense_ffn_backward(saved, cfg, dy, needs):
     return dx, gw1, gb1, gw2, gb2
 
 
-class DenseFFN(torch.autograd.Function):
+class DenseFFN(_ForwardAware):
     """One always-on expert over all tokens: Linear(+b) -> act -> Linear(+b).  The shared expert of `smoe_share` /
     `deepseekv3` (moe_model/model/moe/shard_smoe.py:53, deepseekv3.py:44), the pretrain shared cvmm with an all-zero
     selection (deepseekv2.py:154-165) and each expert of the dense competition pass (competesmoe.py:240-243)."""
 
     @staticmethod
-    def forward(ctx, x2, w1, b1, w2, b2, act: int, layout: int):
-        y, saved, ctx.cfg = dense_ffn_forward(x2, w1, b1, w2, b2, act, layout)
+    def forward(ctx, x2, w1, b1, w2, b2, act: int, layout: int, shared_expert: bool = False):
+        # only a layer's always-on shared expert may take the decode path; the experts of the dense competition pass stay as they are
+        y, saved, ctx.cfg = dense_ffn_forward(x2, w1, b1, w2, b2, act, layout,
+                                              need_backward=not shared_expert or _needs_backward(ctx))
         ctx.save_for_backward(*saved)
         ctx.handoff = _take_handoff()
         return y
@@ -1037,7 +1118,7 @@ class DenseFFN(torch.autograd.Function):
                 # the always-on expert of a shared-expert layer: its dx is the FIRST addend of the routed step's chain (DxHandoff);
                 # this node hands nothing to the engine (None = zero)
                 h.dx, dx = dx, None
-        return dx, gw1, gb1, gw2, gb2, None, None
+        return dx, gw1, gb1, gw2, gb2, None, None, None
 
 
 # ======================================================================================================== affinity

@@ -319,11 +319,12 @@ class MoeLayer(nn.Module):
             + ([f.bias for f in fc2s] if has_b2 else [])
         return CompetitionAffinity.apply(x2, len(self.experts), acts[0], L.B_NK, has_b1, has_b2, fp32_affinity, *params)
 
-    def dense_expert(self, i: int, x):
-        """experts[i](x) over all tokens (shared expert / competition pass)."""
+    def dense_expert(self, i: int, x, shared: bool = False):
+        """experts[i](x) over all tokens (shared expert / competition pass).  `shared`: the always-on expert of a shared-expert
+        layer, which a forward-only call of few rows runs on the decode kernel (competesmoe_amd.decode_rows)."""
         fc1, act, fc2 = parse_expert(self.experts[i])
         B, N, D = x.shape
-        y = DenseFFN.apply(x.reshape(B * N, D), fc1.weight, fc1.bias, fc2.weight, fc2.bias, act, L.B_NK)
+        y = DenseFFN.apply(x.reshape(B * N, D), fc1.weight, fc1.bias, fc2.weight, fc2.bias, act, L.B_NK, shared)
         return y.view(B, N, y.shape[-1])
 
     def forward(self, x, return_id_experts=False):

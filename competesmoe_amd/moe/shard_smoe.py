@@ -36,7 +36,7 @@ class _SharedBase(MoeLayer):
             set_handoff(h)
             routed = self.compute_moe(route.idx, route.w, None, x, n_experts=self.num_of_experts)
             set_handoff(h)
-            shared = self.dense_expert(self.num_of_experts, x)
+            shared = self.dense_expert(self.num_of_experts, x, shared=True)
         finally:
             set_handoff(None)
         return routed, shared, route

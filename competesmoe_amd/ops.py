@@ -619,6 +619,60 @@ def grouped_gemm(A: torch.Tensor, b_ptrs: torch.Tensor, b_layout: int, ldb: int,
     return (Cm, C2) if want_c2 else Cm
 
 
+# ------------------------------------------------------------------------------------------------ decode path (few rows)
+# Largest number of routed rows (T * K) a forward-only call may have to take the weight-streaming grouped GEMM (csrc/gemm_skinny.hip)
+# instead of dispatch + the tiled kernels.  0 = off (the default): every call does exactly what it does without the switch.  Seeded
+# once from CSMOE_DECODE_ROWS; competesmoe_amd.decode_rows(n) sets it.
+_DECODE_ROWS = max(0, int(os.environ.get("CSMOE_DECODE_ROWS", "0") or 0))
+
+
+def decode_rows(n: Optional[int] = None) -> int:
+    """Set (n given) and return the decode-path row limit; 0 switches the path off."""
+    global _DECODE_ROWS
+    if n is not None:
+        if int(n) < 0:
+            raise ValueError("decode_rows: the limit is a row count >= 0 (0 = off)")
+        _DECODE_ROWS = int(n)
+    return _DECODE_ROWS
+
+
+def grouped_gemm_skinny_ok(M: int, N: int, Kd: int, lda: int, ldb: int, ldc: int, b_layout: int, epilogue: int, dtype) -> bool:
+    """Does csmoe_grouped_gemm_skinny take this launch (bf16, forward epilogue, the 8-element / 2 GiB shape rule)?"""
+    dt = L.BF16 if dtype == torch.bfloat16 else L.F32
+    return bool(lib.csmoe_grouped_gemm_skinny_ok(M, N, Kd, lda, ldb, ldc, b_layout, epilogue, dt))
+
+
+def grouped_gemm_skinny(A: torch.Tensor, b_ptrs: torch.Tensor, b_layout: int, ldb: int, N: int, offsets: torch.Tensor, E: int,
+                        bias_ptrs: Optional[torch.Tensor] = None, epilogue: int = L.EPI_PLAIN, act: int = L.ACT_NONE,
+                        want_c2: bool = False, want_c: bool = True, src_rows: Optional[torch.Tensor] = None, src_div: int = 1,
+                        out: Optional[torch.Tensor] = None, out2: Optional[torch.Tensor] = None):
+    """csmoe_grouped_gemm_skinny: the row-space product of grouped_gemm for a call with few rows (forward epilogues, bf16).
+    `src_rows` (int32 [M]): output row m reads A[src_rows[m] // src_div] -- with bins.perm and K the rows dispatch_rows would copy.
+    `out` / `out2`: [M, N] views (unit column stride, the same row stride) to write C / C2 into instead of new tensors."""
+    _need_cuda(A, b_ptrs, offsets, src_rows)
+    if A.stride(1) != 1:
+        raise ValueError("csmoe grouped_gemm_skinny: A must have unit column stride")
+    Kd = A.shape[1]
+    M = A.shape[0] if src_rows is None else src_rows.numel()
+    if src_rows is not None and (src_rows.dtype != torch.int32 or not src_rows.is_contiguous()):
+        raise ValueError("csmoe grouped_gemm_skinny: src_rows must be a contiguous int32 vector")
+    ldc = N
+    for o in (out, out2):
+        if o is not None:
+            if o.shape != (M, N) or o.dtype != A.dtype or o.stride(1) != 1:
+                raise ValueError("csmoe grouped_gemm_skinny: `out` / `out2` must be [M, N] of A's dtype with unit column stride")
+            ldc = o.stride(0)
+    if out is not None and out2 is not None and out.stride(0) != out2.stride(0):
+        raise ValueError("csmoe grouped_gemm_skinny: `out` and `out2` share one row stride")
+    Cm = out if out is not None else (torch.empty(M, N, dtype=A.dtype, device=A.device) if want_c else None)
+    C2 = out2 if out2 is not None else (torch.empty(M, N, dtype=A.dtype, device=A.device) if want_c2 else None)
+    with _timed("grouped_gemm_skinny", 2.0 * M * N * Kd):
+        L.check(lib.csmoe_grouped_gemm_skinny(A.data_ptr(), A.stride(0), _ptr(src_rows), int(src_div), b_ptrs.data_ptr(), b_layout, ldb,
+                                              _ptr(bias_ptrs), offsets.data_ptr(), E, M, N, Kd, _ptr(Cm), _ptr(C2), ldc, epilogue, act,
+                                              _dt(A), _stream()), "grouped_gemm_skinny")
+    return (Cm, C2) if (want_c2 or out2 is not None) else Cm
+
+
 def rowdot_cols(M: int, N: int, Kd: int, lda: int, ldb: int, ldc: int, dtype) -> int:
     """Partial sums per row the EPI_ACTGRAD_ROWSCALE launch of this shape writes into a dot table (0: it would not write one)."""
     return int(lib.csmoe_grouped_gemm_rowdot_cols(M, N, Kd, lda, ldb, ldc, L.BF16 if dtype == torch.bfloat16 else L.F32))

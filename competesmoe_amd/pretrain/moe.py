@@ -276,7 +276,7 @@ class MoE(LoggingLayer, RegularizedLayer, OncePerIterLayer, nn.Module):
             y = DenseFFNFP8.apply(self.operand(x), keys_shared[0], b, values_shared[0], self.act_code, self.fp8_weight_cache,
                                   self.fp8_wgrad)
             return y.view(*shp[:-1], -1)
-        y = DenseFFN.apply(self.operand(x), keys_shared[0], b, values_shared[0], None, self.act_code, L.B_KN)
+        y = DenseFFN.apply(self.operand(x), keys_shared[0], b, values_shared[0], None, self.act_code, L.B_KN, True)
         return y.view(*shp[:-1], -1)
 
     # ------------------------------------------------------------------ losses ([B,N,E]-sized torch math)

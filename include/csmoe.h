@@ -276,6 +276,29 @@ int csmoe_grouped_gemm(const void* A, int64_t lda, const void* const* b_ptrs, in
                        void* C, void* C2, const void* aux, int64_t ldc, int epilogue, int act, int dtype,
                        int kernel, csmoe_stream_t stream);
 
+/* ---- few-row (decode) grouped GEMM ----------------------------------------------------------------------
+ * The row-space product of csmoe_grouped_gemm for a call with FEW rows -- a model in use after training sees T = batch size tokens
+ * per layer, i.e. 2 .. 32 routed rows over up to 64 experts -- where the launch is bound by the bytes of the active experts' weights:
+ * 16-row tiles of one expert on v_mfma_f32_16x16x32_bf16, the weights streamed once per tile straight into registers
+ * (csrc/gemm_skinny.hip).  Same semantics: for every expert e and binned row m in [offsets[e], offsets[e+1])
+ *     C[m, 0:N] = epilogue( A[row(m), 0:Kd] (x) B_e ),   row(m) = src_rows ? src_rows[m] / src_div : m
+ * with B_e = b_ptrs[e] [N,Kd] (CSMOE_B_NK) or [Kd,N] (CSMOE_B_KN), leading dimension ldb.  `src_rows` (int32 [M], may be null)
+ * gathers on the A side: with bins.perm and K it reads the rows csmoe_dispatch_rows would have copied (`x[batch_idx, token_idx]`,
+ * moe_model/model/moe/moe.py:201; cvmm.py:114-119), so a decode step has no dispatch copy.  Any M: an expert with more than 16 rows is
+ * walked in 16-row blocks that each stream the weight slab again, which is why this entry is for few rows and CSMOE_KERNEL_AUTO
+ * never selects it.  Forward epilogues only (PLAIN, BIAS, BIAS_ACT, ROUND_BIAS32_ACT; all six activations; C may be null when only
+ * C2 is wanted), bf16 only.  Shape rule (csmoe_grouped_gemm_skinny_ok, a pure host query returning 0 / 1): N, Kd, lda, ldb, ldc
+ * multiples of 8 (Kd need not be a multiple of 32, N not of 16), operands 16-byte aligned, panels under 2 GiB.
+ * Returns CSMOE_ERR_INVALID for bad arguments; CSMOE_ERR_UNSUPPORTED for fp32, a backward or affinity epilogue, CSMOE_EPI_ACCUM or a
+ * shape the rule rejects -- decided before any pointer is read and before anything is launched, so nothing is written; M == 0 is
+ * CSMOE_OK.  K is split over the 8 waves of a workgroup and summed in wave order: no atomics, bit-identical from run to run.
+ * replaces, for few rows: cvmm_kernel (moe_pretrain_model/layers/cvmm.py:61-168) and the per-expert nn.Linear calls of compute_moe
+ * (moe_model/model/moe/moe.py:196-204) -- the path `generate` takes through the layer at decode time. */
+int csmoe_grouped_gemm_skinny(const void* A, int64_t lda, const int32_t* src_rows, int src_div, const void* const* b_ptrs,
+                              int b_layout, int64_t ldb, const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N,
+                              int Kd, void* C, void* C2, int64_t ldc, int epilogue, int act, int dtype, csmoe_stream_t stream);
+int csmoe_grouped_gemm_skinny_ok(int M, int N, int Kd, int64_t lda, int64_t ldb, int64_t ldc, int b_layout, int epilogue, int dtype);
+
 /* partial sums per row written into the dot table of CSMOE_EPI_ACTGRAD_ROWSCALE for this launch shape; 0: no table (generic kernel) */
 int csmoe_grouped_gemm_rowdot_cols(int M, int N, int Kd, int64_t lda, int64_t ldb, int64_t ldc, int dtype);
 
