@@ -56,6 +56,12 @@ int k_quantize_mxfp8_tokens(const void* x, int64_t ldx, const int32_t* offsets, 
 int gg8f_wgrad(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Bq, int64_t ldb, const void* Bs, int64_t ldbs,
                const int32_t* poff, int E, int Na, int Nb, void* const* c_ptrs, int64_t ldc, int out_dtype, int accumulate,
                const int32_t* xcd_order, hipStream_t st);
+bool gg_skinny8_shape_ok(int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc, int64_t ldcq, int64_t ldcs, int M, int N,
+                         int Kd, int quant_out);
+int gg_skinny8_rowspace(const void* Aq, int64_t lda, const void* As, int64_t ldas, const int32_t* src_rows, int src_div,
+                        const void* const* bq_ptrs, const void* const* bs_ptrs, int64_t ldb, int64_t ldbs,
+                        const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2,
+                        int64_t ldc, void* Cq, void* Cs, int64_t ldcq, int64_t ldcs, int epilogue, int act, hipStream_t st);
 int k_router_select(const void*, int, int, int, int, int, int, float, float*, int32_t*, float*, hipStream_t);
 int k_router_select_bwd(const void*, int, int, int, int, int, int, float, const float*, const int32_t*, const float*, const float*,
                         const float*, void*, hipStream_t);
@@ -792,6 +798,52 @@ int csmoe_dense_gemm_mxfp8(const void* Aq, int64_t lda, const void* As, int64_t 
   if (int rc = fp8_shape_ok(lda, ldas, ldb, ldbs, ldc, N, Kd, Aq, C ? C : C2, "dense_gemm_mxfp8")) return rc;
   return gg8f_rowspace(Aq, lda, As, ldas, nullptr, nullptr, ldb, ldbs, nullptr, nullptr, 1, M, N, Kd, C, C2, aux, ldc, epilogue, act,
                        Bq, Bs, bias, (hipStream_t)stream);
+}
+
+
+// ---- few-row (decode) grouped GEMM on MXFP8 operands: gemm_skinny_fp8.hip.  As for csmoe_grouped_gemm_skinny, refusals
+// (CSMOE_ERR_UNSUPPORTED) come before any pointer is looked at and before anything is launched.
+static bool skinny8_epilogue_ok(int epilogue) {
+  return epilogue == CSMOE_EPI_PLAIN || epilogue == CSMOE_EPI_BIAS || epilogue == CSMOE_EPI_BIAS_ACT;
+}
+
+int csmoe_grouped_gemm_skinny_mxfp8_ok(int M, int N, int Kd, int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc,
+                                       int64_t ldcq, int64_t ldcs, int epilogue, int quant_out) {
+  if (!skinny8_epilogue_ok(epilogue) || (quant_out && epilogue != CSMOE_EPI_BIAS_ACT)) return 0;
+  if (M < 0 || N <= 0 || Kd <= 0 || lda < Kd || ldb < Kd || ldc < N || ldas < Kd / 32 || ldbs < Kd / 32) return 0;
+  if (quant_out && (ldcq < N || ldcs < N / 32)) return 0;
+  return gg_skinny8_shape_ok(lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, M, N, Kd, quant_out) ? 1 : 0;
+}
+
+int csmoe_grouped_gemm_skinny_mxfp8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const int32_t* src_rows, int src_div,
+                                    const void* const* bq_ptrs, const void* const* bs_ptrs, int64_t ldb, int64_t ldbs,
+                                    const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C,
+                                    void* C2, int64_t ldc, void* Cq, void* Cs, int64_t ldcq, int64_t ldcs, int epilogue, int act,
+                                    csmoe_stream_t stream) {
+  CSMOE_CHECK_ARG(epilogue >= 0 && epilogue <= CSMOE_EPI_ACCUM && act >= 0 && act <= 5, "grouped_gemm_skinny_mxfp8: bad epilogue/act");
+  CSMOE_CHECK_ARG(!src_rows || src_div > 0, "grouped_gemm_skinny_mxfp8: src_div = %d must be positive", src_div);
+  CSMOE_CHECK_ARG(!Cq == !Cs, "grouped_gemm_skinny_mxfp8: the quantised output needs both Cq and Cs");
+  if (epilogue == CSMOE_EPI_ACCUM) return accum_unsupported("grouped_gemm_skinny_mxfp8");
+  if (!skinny8_epilogue_ok(epilogue)) {
+    csmoe_set_error("grouped_gemm_skinny_mxfp8: forward epilogues only (PLAIN, BIAS, BIAS_ACT), got %d", epilogue);
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  CSMOE_CHECK_ARG(!Cq || epilogue == CSMOE_EPI_BIAS_ACT, "grouped_gemm_skinny_mxfp8: Cq / Cs go with the BIAS_ACT epilogue");
+  CSMOE_CHECK_ARG(E > 0 && M >= 0 && N > 0 && Kd > 0, "grouped_gemm_skinny_mxfp8: bad shape E=%d M=%d N=%d Kd=%d", E, M, N, Kd);
+  CSMOE_CHECK_ARG(lda >= Kd && ldb >= Kd && ldc >= N && ldas >= Kd / 32 && ldbs >= Kd / 32 && (!Cq || (ldcq >= N && ldcs >= N / 32)),
+                  "grouped_gemm_skinny_mxfp8: leading dimension too small");
+  CSMOE_CHECK_ARG(bq_ptrs && bs_ptrs && offsets, "grouped_gemm_skinny_mxfp8: null pointer table / offsets");
+  if (M == 0) return CSMOE_OK;
+  CSMOE_CHECK_ARG(Aq && As && (C || (epilogue == CSMOE_EPI_BIAS_ACT && (C2 || Cq))), "grouped_gemm_skinny_mxfp8: null pointer");
+  if (!gg_skinny8_shape_ok(lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, M, N, Kd, Cq != nullptr) || ((uintptr_t)Aq & 15) ||
+      ((uintptr_t)As & 3) || ((uintptr_t)C & 15) || ((uintptr_t)C2 & 15) || ((uintptr_t)Cq & 7)) {
+    csmoe_set_error("grouped_gemm_skinny_mxfp8: needs Kd %% 128 == 0, N %% 8 == 0 (N %% 32 == 0 with Cq), lda, ldb multiples of 16, "
+                    "ldas, ldbs of 4, ldc, ldcq of 8, 16-byte aligned operands (As: 4-byte) and panels under 2 GiB "
+                    "(csmoe_grouped_gemm_skinny_mxfp8_ok); M=%d N=%d Kd=%d", M, N, Kd);
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  return gg_skinny8_rowspace(Aq, lda, As, ldas, src_rows, src_div, bq_ptrs, bs_ptrs, ldb, ldbs, bias_ptrs, offsets, E, M, N, Kd, C, C2,
+                             ldc, Cq, Cs, ldcq, ldcs, epilogue, act, (hipStream_t)stream);
 }
 
 

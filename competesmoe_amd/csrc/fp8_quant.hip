@@ -5,32 +5,13 @@
 //   rows:       x [R, C] -> q [R, C] u8, s [R, C/32] u8          (blocks along the contiguous dim: activations, K-contiguous weights)
 //   transposed: x [R, C] -> q [C, R] u8, s [C, R/32] u8          (blocks along dim 0: the same weights for the transposed product)
 // Inputs bf16 or fp32 (the pretrain stack's fp32 master weights are quantised directly: no bf16 cast pass).
-#include "common.h"
+// The scale-and-convert device code (e8m0_of_amax, inv_scale_of, sat448, pack4_e4m3) lives in mx_quant.h, shared with the fused
+// quantised output of gemm_skinny_fp8.hip.
+#include "mx_quant.h"
 #include <algorithm>
 #include <type_traits>
 
 namespace {
-
-__device__ __forceinline__ int e8m0_of_amax(float amax) {
-  // biased exponent byte of 2^(floor(log2(amax)) - 8); amax == 0 (or subnormal) -> the smallest scale
-  const int be = (int)((__float_as_uint(amax) >> 23) & 0xff);      // floor(log2(amax)) + 127 for normal amax
-  const int s = be - 8;
-  return s < 0 ? 0 : (s > 254 ? 254 : s);
-}
-__device__ __forceinline__ float inv_scale_of(int sbyte) {         // 2^-(sbyte - 127), exact
-  const int e = 254 - sbyte;                                       // biased exponent of the reciprocal
-  return e <= 0 ? __uint_as_float(0x00400000u >> (-e)) : __uint_as_float((unsigned)e << 23);
-}
-// saturate to +-448 but let a NaN through (fminf / fmaxf return their non-NaN operand, which would turn NaN into -448): the
-// conversion below encodes it as the e4m3 NaN, so a NaN activation still poisons its output row as it does on the bf16 path
-__device__ __forceinline__ float sat448(float v) { return v != v ? v : fminf(fmaxf(v, -448.f), 448.f); }
-__device__ __forceinline__ unsigned pack4_e4m3(float a, float b, float c, float d) {
-  a = sat448(a); b = sat448(b); c = sat448(c); d = sat448(d);
-  int w = 0;
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  return (unsigned)w;
-}
 
 template <typename T> __device__ __forceinline__ void load32(const T* p, float (&v)[32]);
 template <> __device__ __forceinline__ void load32<bf16>(const bf16* p, float (&v)[32]) {

@@ -1302,21 +1302,41 @@ def fp8_weight_cache_clear():
     _FP8_WCACHE.clear()
 
 
+def _fp8_wcache_put(key, t: torch.Tensor, first: bool, out) -> None:
+    if first:                                                  # first entry under this key: it goes when its owner is freed
+        import weakref
+        owner = t._base if t._base is not None else t          # `keys_shared[0]` is a fresh view per call: the parameter owns the entry
+        weakref.finalize(owner, _FP8_WCACHE.pop, key, None)
+    _FP8_WCACHE[key] = (t._version, out)
+
+
 def _quantize_weight_both(t: torch.Tensor, cache: bool):
     """((q, s) blocks along the last dim, (qt, st) blocks along the second-to-last) of a master weight tensor [.., R, C]."""
     if not cache:
         return ops.quantize_mxfp8_both(t)
     key = (t.data_ptr(), tuple(t.shape), t.dtype)
     hit = _FP8_WCACHE.get(key)
-    if hit is not None and hit[0] == t._version:
+    if hit is not None and hit[0] == t._version and hit[1][0] is not None:
         return hit[1]
-    out = ops.quantize_mxfp8_both(t)
-    if hit is None:                                            # first entry under this key: it goes when its owner is freed
-        import weakref
-        owner = t._base if t._base is not None else t          # `keys_shared[0]` is a fresh view per call: the parameter owns the entry
-        weakref.finalize(owner, _FP8_WCACHE.pop, key, None)
-    _FP8_WCACHE[key] = (t._version, out)
+    out = ops.quantize_mxfp8_both(t)                           # also replaces a forward-only entry (_quantize_weight_fwd)
+    _fp8_wcache_put(key, t, hit is None, out)
     return out
+
+
+def _quantize_weight_fwd(t: torch.Tensor, cache: bool):
+    """The forward half (qt, st) of _quantize_weight_both alone, for a call that cannot have a backward: the backward orientation (a
+    second copy of the table) is neither built nor kept.  The forward half of a current "both" entry if there is one; else
+    quantize_mxfp8(transpose=True) -- bit-identical to that half (include/csmoe.h) -- cached as a forward-only entry (None, (qt, st))
+    of this parameter version, which a later call that needs both orientations replaces."""
+    if not cache:
+        return ops.quantize_mxfp8(t, transpose=True)
+    key = (t.data_ptr(), tuple(t.shape), t.dtype)
+    hit = _FP8_WCACHE.get(key)
+    if hit is not None and hit[0] == t._version:
+        return hit[1][1]
+    fwd = ops.quantize_mxfp8(t, transpose=True)
+    _fp8_wcache_put(key, t, hit is None, (None, fwd))
+    return fwd
 
 
 def _wgrad_fp8_out_dtype(pd):
@@ -1357,15 +1377,44 @@ def _dense_wgrad_fp8(at, ats, bt, bts, poff, M: int, out_dtype) -> torch.Tensor:
     return ops.dense_colsum(part.view(P, Na * Nb), out_dtype=out_dtype).view(Na, Nb)
 
 
-class MoEFFNPackedFP8(torch.autograd.Function):
+def _fp8_decode_ok(n: int, D: int, F: int, Dout: int) -> bool:
+    """Both GEMMs of a forward-only fp8 call with n rows fit csmoe_grouped_gemm_skinny_mxfp8 (the first with its quantised output).
+    Their operands are tensors the path allocates itself (contiguous, aligned), so the shapes decide; D % 128 == 0 also gives the
+    quantiser of x its D % 32 == 0."""
+    return (ops.grouped_gemm_skinny_mxfp8_ok(n, F, D, epilogue=L.EPI_BIAS_ACT, quant_out=True)
+            and ops.grouped_gemm_skinny_mxfp8_ok(n, Dout, F, epilogue=L.EPI_PLAIN))
+
+
+def _ffn_fp8_decode(x2, w1, w2, b1, act: int, offsets, src_rows, src_div: int):
+    """The two expert GEMMs of a forward-only fp8 call with few rows, on the weight-streaming kernel (csrc/gemm_skinny_fp8.hip):
+    the T token rows are quantised where they lie (per row: quantise-then-gather is gather-then-quantise, so there is no dispatch
+    copy), GEMM 1 gathers through `src_rows` and writes only the MXFP8 form of the activated output (no pre-activation, no bf16
+    hact, no quantiser launch), GEMM 2 reads it.  w1 [E, D, F] / w2 [E, F, Dout] (or 2-D: one expert) are masters whose forward
+    tables come from the weight cache (_quantize_weight_fwd); b1 [E, F] / [F] or None.  Returns y [M, Dout] bf16 in binned order."""
+    b1_ptrs = None
+    if b1 is not None:
+        b_op = b1.to(torch.bfloat16).contiguous()              # alive until GEMM 1 is enqueued
+        b1_ptrs = ops.ptr_table(b_op, b_op.numel() // b_op.shape[-1], b_op.shape[-1] * 2)
+    xq, xsc = ops.quantize_mxfp8(x2)
+    kq, ks = _quantize_weight_fwd(w1, True)                    # [E, F, D], scales along D
+    vq, vs = _quantize_weight_fwd(w2, True)                    # [E, Dout, F], scales along F
+    if kq.dim() == 2:
+        kq, ks, vq, vs = kq[None], ks[None], vq[None], vs[None]
+    _, _, hq, hs = ops.grouped_gemm_skinny_mxfp8(xq, xsc, kq, ks, offsets, bias_ptrs=b1_ptrs, epilogue=L.EPI_BIAS_ACT, act=act,
+                                                 want_c=False, want_q=True, src_rows=src_rows, src_div=src_div)
+    return ops.grouped_gemm_skinny_mxfp8(hq, hs, vq, vs, offsets)
+
+
+class MoEFFNPackedFP8(_ForwardAware):
     """MoEFFNPacked with the four row-space expert GEMMs of a step (GEMM 1, GEMM 2, dH, dXs) on the block-scaled fp8 matrix pipe
     (BASELINE config 5; `csmoe_grouped_gemm_mxfp8`): operands quantised to MXFP8 (e4m3 + one e8m0 scale per 32 elements along each
     GEMM's reduction dim), fp32 accumulation, bf16 results.  The weight gradients stay bf16 products of the bf16 activations
     (`csmoe_grouped_wgrad`) unless `wgrad_fp8`: then they run on the fp8 pipe too (`csmoe_grouped_wgrad_mxfp8`), with the activations
     and dy / dh quantised along the token dim inside every expert's rows (`csmoe_quantize_mxfp8_tokens`; dy and dh in the same pass
     as their row orientation); everything else the backward returns is unchanged, bit for bit.  Master weights (fp32 or bf16) are quantised directly, once per use and orientation -- there is no
-    bf16 operand copy -- or, with `cache`, once per parameter version (_quantize_weight_both).  No counterpart upstream (the
-    reference has no fp8): checked against oracle/mxfp8.py, tests/test_fp8_gpu.py."""
+    bf16 operand copy -- or, with `cache`, once per parameter version (_quantize_weight_both).  A call that needs no backward, with
+    `cache` and at most ops.decode_rows() routed rows, takes the decode path (_ffn_fp8_decode).  No counterpart upstream (the
+    reference has no fp8): checked against oracle/mxfp8.py, tests/test_fp8_gpu.py, tests/test_decode_fp8_path_gpu.py."""
 
     @staticmethod
     def forward(ctx, x2, w, idx, keys, values, bias, act: int, combine_mode: int, cache: bool = False, wgrad_fp8: bool = False):
@@ -1376,6 +1425,11 @@ class MoEFFNPackedFP8(torch.autograd.Function):
         E, D, F = keys.shape
         T = x2.shape[0]
         bins = ops.bin_tokens(idx, E)
+        if (not _needs_backward(ctx) and cache and 0 < bins.n <= ops.decode_rows()
+                and _fp8_decode_ok(bins.n, D, F, values.shape[2])):
+            y = _ffn_fp8_decode(x2, keys, values, bias, act, bins.offsets, bins.perm, bins.K)
+            ctx.saved = None                     # no backward can follow
+            return ops.combine(y, bins, idx, w, combine_mode, T)
         xs, xq, xsc = ops.dispatch_tokens_mxfp8(x2, bins)       # the gather and the quantiser in one pass (CSMOE_DISPATCH_QUANT=0: two)
         (kq_b, ks_b), (kq, ks) = _quantize_weight_both(keys, cache)        # backward pair [E, D, F]; forward pair [E, F, D] (reduction over D)
         b_op = b1 = None
@@ -1450,13 +1504,18 @@ class MoEFFNPackedFP8(torch.autograd.Function):
         return dx2, dw, None, gk, gv, gb, None, None, None, None
 
 
-class DenseFFNFP8(torch.autograd.Function):
+class DenseFFNFP8(_ForwardAware):
     """The always-on shared expert on the same fp8 pipe: x [T, D] -> act(x @ w1 [D, Fs] (+ b1)) @ w2 [Fs, Dout] (packed layout of
     the pretrain stack's `keys_shared[0]` / `values_shared[0]`, deepseekv2.py:97-105).  `wgrad_fp8`: the weight gradients on the fp8
     pipe as in MoEFFNPackedFP8 (one expert: E = 1)."""
 
     @staticmethod
     def forward(ctx, x2, w1, b1, w2, act: int, cache: bool = False, wgrad_fp8: bool = False):
+        T, D = x2.shape
+        if (not _needs_backward(ctx) and cache and 0 < T <= ops.decode_rows() and x2.dtype == torch.bfloat16):
+            x2 = x2.contiguous()
+            if _fp8_decode_ok(T, D, w1.shape[1], w2.shape[1]):         # the decode path of MoEFFNPackedFP8 with E = 1
+                return _ffn_fp8_decode(x2, w1, w2, b1, act, ops.dense_offsets(T, x2.device), None, 1)
         y, saved, ctx.cfg = dense_ffn_fp8_forward(x2, w1, b1, w2, act, cache)
         ctx.save_for_backward(*saved)
         ctx.wgrad_fp8 = bool(wgrad_fp8)

@@ -473,6 +473,33 @@ int csmoe_grouped_gemm_mxfp8(const void* Aq, int64_t lda, const void* As, int64_
 int csmoe_dense_gemm_mxfp8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Bq, const void* Bs, int64_t ldb,
                            int64_t ldbs, const void* bias, int M, int N, int Kd, void* C, void* C2, const void* aux, int64_t ldc,
                            int epilogue, int act, csmoe_stream_t stream);
+/* Few-row (decode) form of csmoe_grouped_gemm_mxfp8 (csrc/gemm_skinny_fp8.hip): the weight streamer of csmoe_grouped_gemm_skinny
+ * on MXFP8 operands, one v_mfma_scale_f32_16x16x128_f8f6f4 per 128-element K-step, the weights (half the bytes of bf16) read once
+ * per 16-row block straight into registers.  For every expert e and binned row m in [offsets[e], offsets[e+1])
+ *     C[m, 0:N] = epilogue( sum_k dq(A)[row(m), k] dq(B_e)[n, k] ),   row(m) = src_rows ? src_rows[m] / src_div : m
+ * A = Aq [R, Kd] e4m3 (lda) with scales As [R, Kd/32] (ldas): one source row supplies its elements and its scale row, so with
+ * bins.perm and K the call reads the T quantised token rows and no dispatch copy exists.  B_e = bq_ptrs[e] [N, Kd] e4m3 (ldb) with
+ * scales bs_ptrs[e] [N, Kd/32] (ldbs): the one weight layout of csmoe_grouped_gemm_mxfp8; every bq_ptrs[e] 16-byte and every
+ * bs_ptrs[e] 4-byte aligned (device tables: the caller's contract, the entry cannot look).  bf16 outputs and biases;
+ * epilogues PLAIN, BIAS, BIAS_ACT (all six activations) at the rounding points of csmoe_grouped_gemm_mxfp8; C may be null when only
+ * the activated output is wanted.
+ * Fused MXFP8 output (BIAS_ACT only; Cq and Cs both null or both given): Cq [M, N] e4m3 (ldcq) and Cs [M, N/32] e8m0 (ldcs) receive
+ * the MX quantisation of the bf16-ROUNDED activated output, blocks along N -- byte for byte what csmoe_quantize_mxfp8 (transpose = 0)
+ * writes for C2 -- and C2 may then be null: the operand of the second product without a quantiser launch and without a bf16 write.
+ * Shape rule (csmoe_grouped_gemm_skinny_mxfp8_ok, a pure host query returning 0 / 1; ldcq / ldcs are looked at only with
+ * quant_out): Kd % 128 == 0, N % 8 == 0, lda % 16 == 0, ldb % 16 == 0, ldas % 4 == 0, ldbs % 4 == 0, ldc % 8 == 0; with the quantised
+ * output N % 32 == 0 and ldcq % 8 == 0; Aq / C / C2 16-byte, Cq 8-byte and As 4-byte aligned (scale bytes are read a word at a time); M * lda and N * ldb under 2 GiB.
+ * Returns CSMOE_ERR_INVALID for bad arguments (null tables, src_div <= 0, Cq without BIAS_ACT); CSMOE_ERR_UNSUPPORTED for a backward
+ * epilogue, CSMOE_EPI_ACCUM or a shape the rule rejects -- decided before any pointer is read and before anything is launched;
+ * M == 0 is CSMOE_OK.  K is split over the 8 waves of a workgroup and summed in wave order: no atomics, bit-identical from run to
+ * run.  No counterpart upstream (the reference has no fp8). */
+int csmoe_grouped_gemm_skinny_mxfp8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const int32_t* src_rows, int src_div,
+                                    const void* const* bq_ptrs, const void* const* bs_ptrs, int64_t ldb, int64_t ldbs,
+                                    const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C,
+                                    void* C2, int64_t ldc, void* Cq, void* Cs, int64_t ldcq, int64_t ldcs, int epilogue, int act,
+                                    csmoe_stream_t stream);
+int csmoe_grouped_gemm_skinny_mxfp8_ok(int M, int N, int Kd, int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc,
+                                       int64_t ldcq, int64_t ldcs, int epilogue, int quant_out);
 
 /* ---- MXFP8 weight gradients: operands quantised along the TOKEN dimension -------------------------------------------------
  * Blocking contract.  A block is 32 consecutive BINNED rows of ONE expert.  Binned order is that of csmoe_bin_tokens (a stable

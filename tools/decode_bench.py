@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Decode-time expert GEMMs: the weight-streaming kernel (csmoe_grouped_gemm_skinny, gather folded into the first product) against
 the same two products through csmoe_grouped_gemm(kernel=AUTO) behind a dispatch_tokens copy -- what a layer call does without
-the decode switch.  usage: python tools/decode_bench.py [--reps 30] [--out table.md]
+the decode switch.  usage: python tools/decode_bench.py [--reps 30] [--out table.md] [--dtype bf16|fp8]
 
 Grid: T in {1 .. 256} tokens, K = 2, at the headline dimensions (D 4096, F 11008, 64 experts) and at the SigLIP layer's (1152 / 4304,
 4 experts), both weight layouts (B_NK with GELU as the LLaVA stack runs it, B_KN with ReLU as the pretrain stack does).  Both paths
@@ -12,7 +12,14 @@ reads was last touched more than 256 MiB (the Infinity Cache) of other weights a
 
 The calls are bound by bandwidth: `GB` is the algorithmic weight traffic of a repetition (the two matrices of every expert that
 received a row, bf16, read once), `% HBM` that traffic per second of the new path over the 8.0 TB/s HBM3E peak of the MI355X
-(6.3 TB/s is what a copy kernel reaches)."""
+(6.3 TB/s is what a copy kernel reaches).
+
+--dtype fp8 (the fp8 layers, `args.fp8_experts`): at the headline dimensions and at BASELINE config 5's (128 experts) three chains
+are timed the same way, each in its own series of one process: the fp8 decode chain (quantize_mxfp8 of the T rows + two
+csmoe_grouped_gemm_skinny_mxfp8 launches, the first gathering and writing the MXFP8 hidden activations), the tiled fp8 chain the
+layer runs without the switch (dispatch_tokens_mxfp8 + grouped_gemm_mxfp8 + quantize_mxfp8 + grouped_gemm_mxfp8), and the bf16
+decode chain at the same dimensions (B_KN, ReLU: the pretrain stack).  `+-` is half the interquartile range of the repetitions;
+the fp8 weight traffic counts one byte per element plus the scale bytes (1 / 32)."""
 import argparse
 import os
 import statistics
@@ -26,7 +33,7 @@ from competesmoe_amd import ops, _lib as L  # noqa: E402
 DEV = "cuda"
 HBM_PEAK = 8.0e12
 TS = (1, 2, 4, 8, 16, 32, 64, 128, 256)
-DIMS = {"headline": (4096, 11008, 64), "siglip": (1152, 4304, 4)}
+DIMS = {"headline": (4096, 11008, 64), "siglip": (1152, 4304, 4), "config5": (4096, 11008, 128)}
 K = 2
 
 
@@ -88,12 +95,124 @@ def bench_case(sets, D, F, E, layout, T, reps, warm):
     return ms["new"], ms["old"], act_med * 2 * D * F * 2
 
 
+def weight_sets_fp8(D, F, E):
+    """Copies of the two MXFP8 forward tables ([E, F, D] / [E, D, F] e4m3 with scales along the last dim): finite random bytes."""
+    one = 2 * E * D * F
+    n = max(3, min(12, -(-(3 * 256 << 20) // one)))        # at least 3: two chains read these, and never the same copy in a repetition
+
+    def mk(rows, cols):
+        q = torch.randint(0, 120, (E, rows, cols), device=DEV, dtype=torch.uint8)
+        q += torch.randint(0, 2, (E, rows, cols), device=DEV, dtype=torch.uint8) * 128
+        return q, torch.randint(112, 118, (E, rows, cols // 32), device=DEV, dtype=torch.uint8)
+    return [(mk(F, D), mk(D, F)) for _ in range(n)]
+
+
+def _med_spread(events):
+    ms = sorted(a.elapsed_time(b) for a, b in events)
+    q = statistics.quantiles(ms, n=4)
+    return statistics.median(ms), (q[2] - q[0]) / 2
+
+
+def bench_case_fp8(sets8, sets16, D, F, E, T, reps, warm):
+    """(median ms, spread) of the fp8 decode chain, the tiled fp8 chain and the bf16 decode chain, and the active experts."""
+    g = torch.Generator().manual_seed(1000 * T + 8)
+    x = torch.randn(T, D, generator=g).bfloat16().to(DEV)
+    total = reps + 5
+    routes = []
+    for r in range(total):
+        idx = torch.rand(T, E, generator=g).topk(K, -1).indices.int()
+        if warm and routes:
+            idx = routes[0][0].cpu()
+        active = int(idx.unique().numel())
+        idx = idx.to(DEV)
+        routes.append((idx, ops.bin_tokens(idx, E), active))
+    tabs16 = [(ops.ptr_table(w1, E, D * F * 2), ops.ptr_table(w2, E, D * F * 2)) for w1, w2 in sets16]
+
+    def new8(bins, t):
+        (kq, ks), (vq, vs) = t
+        xq, xs = ops.quantize_mxfp8(x)
+        _, _, hq, hs = ops.grouped_gemm_skinny_mxfp8(xq, xs, kq, ks, bins.offsets, epilogue=L.EPI_BIAS_ACT, act=L.ACT_RELU, want_c=False,
+                                                     want_q=True, src_rows=bins.perm, src_div=K)
+        ops.grouped_gemm_skinny_mxfp8(hq, hs, vq, vs, bins.offsets)
+
+    def old8(bins, t):
+        (kq, ks), (vq, vs) = t
+        _, xq, xs = ops.dispatch_tokens_mxfp8(x, bins)
+        _, h = ops.grouped_gemm_mxfp8(xq, xs, kq, ks, bins.offsets, epilogue=L.EPI_BIAS_ACT, act=L.ACT_RELU, want_c2=True, want_c=False)
+        hq, hs = ops.quantize_mxfp8(h)
+        ops.grouped_gemm_mxfp8(hq, hs, vq, vs, bins.offsets)
+
+    def new16(bins, t):
+        _, h = ops.grouped_gemm_skinny(x, t[0], L.B_KN, F, F, bins.offsets, E, epilogue=L.EPI_BIAS_ACT, act=L.ACT_RELU, want_c2=True,
+                                       want_c=False, src_rows=bins.perm, src_div=K)
+        ops.grouped_gemm_skinny(h, t[1], L.B_KN, D, D, bins.offsets, E)
+
+    # (name, chain, its weight copies, copies a repetition advances by, offset of this chain): cold, the two fp8 chains of
+    # repetition r read fp8 copies 2 r and 2 r + 1 (mod n >= 3: never the same one, and a copy's next use comes after the other
+    # copies' traffic), the bf16 chain its own copy r
+    chains = (("new8", new8, sets8, 2, 0), ("old8", old8, sets8, 2, 1), ("new16", new16, tabs16, 1, 0))
+    ev = {c[0]: [] for c in chains}
+    for r, (idx, bins, active) in enumerate(routes):
+        for j in range(3):
+            name, fn, pool, step, own = chains[(r + j) % 3]
+            t = pool[0] if warm else pool[(step * r + own) % len(pool)]
+            e = timed(lambda: fn(bins, t))
+            if r >= 5:
+                ev[name].append(e)
+    torch.cuda.synchronize()
+    return {k: _med_spread(v) for k, v in ev.items()}, statistics.median(a for _, _, a in routes[5:])
+
+
+def main_fp8(a):
+    lines = [f"device: {torch.cuda.get_device_name(0)}; reps {a.reps}, median +- half the interquartile range; K = {K}; ReLU", "",
+             "| dims | T | rows | cold fp8 decode ms | cold fp8 tiled ms | tiled/decode | cold bf16 decode ms | bf16/fp8 decode | fp8 GB | "
+             "fp8 decode GB/s | % of 8.0 TB/s | bf16 decode GB/s | % of 8.0 TB/s | warm fp8 decode ms | warm fp8 tiled ms |",
+             "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for name in a.dims.split(","):
+        D, F, E = DIMS[name]
+        sets8 = weight_sets_fp8(D, F, E)
+        sets16 = [(torch.randn(E, D * F, device=DEV, dtype=torch.bfloat16) * 0.02, torch.randn(E, D * F, device=DEV, dtype=torch.bfloat16) * 0.02)
+                  for _ in range(2)]
+        for T in TS:
+            cold, active = bench_case_fp8(sets8, sets16, D, F, E, T, a.reps, warm=False)
+            warm, _ = bench_case_fp8(sets8, sets16, D, F, E, T, a.reps, warm=True)
+            b8, b16 = active * 2 * D * F * (1 + 1 / 32), active * 2 * D * F * 2
+            (n8, sn8), (o8, so8), (n16, sn16) = cold["new8"], cold["old8"], cold["new16"]
+            bw8, bw16 = b8 / (n8 * 1e-3), b16 / (n16 * 1e-3)
+            lines.append(f"| {name} | {T} | {T * K} | {n8:.4f} +- {sn8:.4f} | {o8:.4f} +- {so8:.4f} | {o8 / n8:.2f} | {n16:.4f} +- {sn16:.4f} | "
+                         f"{n16 / n8:.2f} | {b8 / 1e9:.3f} | {bw8 / 1e9:.0f} | {100 * bw8 / HBM_PEAK:.1f} | {bw16 / 1e9:.0f} | "
+                         f"{100 * bw16 / HBM_PEAK:.1f} | {warm['new8'][0]:.4f} | {warm['old8'][0]:.4f} |")
+            print(lines[-1], flush=True)
+        del sets8, sets16
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--dims", default="headline,siglip")
+    ap.add_argument("--dims", default=None, help="default: headline,siglip (bf16) / headline,config5 (fp8)")
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.dims = a.dims or ("headline,config5" if a.dtype == "fp8" else "headline,siglip")
+    for name in a.dims.split(","):
+        if name not in DIMS:
+            ap.error(f"unknown dims '{name}'; choose from {', '.join(DIMS)}")
+        D, F, _ = DIMS[name]
+        if a.dtype == "fp8" and (D % 128 or F % 128):
+            ap.error(f"--dtype fp8: dims '{name}' (D = {D}, F = {F}) are no multiples of 128, which the MXFP8 kernels need for both "
+                     "reduction dims; choose from headline, config5")
+    lines = main_fp8(a) if a.dtype == "fp8" else main_bf16(a)
+    text = "\n".join(lines) + "\n"
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text)
+    print(text)
+
+
+def main_bf16(a):
     lines = [f"device: {torch.cuda.get_device_name(0)}; reps {a.reps}, median; K = {K}", "",
              "| dims | layout | T | rows | cold new ms | cold old ms | old/new | GB (active weights) | cold new GB/s | % of 8.0 TB/s | warm new ms | warm old ms |",
              "|---|---|---|---|---|---|---|---|---|---|---|---|"]
@@ -110,12 +229,7 @@ def main():
                 print(lines[-1], flush=True)
         del sets
         torch.cuda.empty_cache()
-    text = "\n".join(lines) + "\n"
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text)
-    print(text)
+    return lines
 
 
 if __name__ == "__main__":
