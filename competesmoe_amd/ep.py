@@ -19,6 +19,13 @@ all outbound exchanges are queued at once, the grouped GEMMs of group c start as
 back while group c+1 is in the GEMMs.  Exposed communication drops from 2 (4 in the backward) full exchanges to about 1/chunks of
 them.  chunks = 1 is the plain path (one blocking all_to_all_single each way).
 
+One exchange lane, one local step: a group of local experts is a `_Lane` (send / arrived / give_back; per-peer messages + a regroup
+pass, or `direct`: one message per (peer, local expert) that lands expert-major) under every overlapped function -- EPFFNChunked
+for the LLaVA stack's module experts, EPFFNPacked / EPFFNPackedFP8 / EPFFNPackedSlots for the packed experts of the pretrain stack
+-- and under EPFFN's direct road.  Between the trips EPFFN and EPFFNChunked call the same helpers (`_local_ffn`, `_local_dh`,
+`_local_dxs`, `_local_wgrads`); the packed functions take their preludes (operand tables, fp8 input checks, the second-backward
+error) from functional.py, where the single-GPU functions they mirror row for row take them too.
+
 Everything that touches `torch.distributed` is in the small functions at the top so the plumbing is testable with `gloo`
 on CPU (tests/test_ep_gloo.py); the compute between the exchanges is the same HIP kernels as the single-GPU path.
 """
@@ -33,8 +40,10 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import _lib as L
+from . import functional as Fn
 from . import ops
-from .functional import ExpertTable, _grouped_colsum
+from .functional import (CompetitionAffinityPacked, DenseFFN, ExpertTable, RouterSelect, SoftplusMean, _SlotMap, _grouped_colsum,
+                         _module_grads, _take_saved)
 from .moe.moe import MoeLayer
 from .moe.register import register_moe
 
@@ -234,233 +243,6 @@ class _Unsort:
         self.perm, self.K, self.n = bins.slot_of, 1, bins.n
 
 
-class EPFFN(torch.autograd.Function):
-    """dispatch -> all-to-all -> local grouped FFN -> all-to-all -> combine, and the mirrored backward."""
-
-    @staticmethod
-    def forward(ctx, x2, w, idx, tab: ExpertTable, E_global: int, group, combine_mode: int, want_slots: bool, direct: bool, *params):
-        """Returns (out [T, Dout], y_tk): the combined output and, with `want_slots`, the expert outputs per (token, k) slot in flat
-        order [T*K, Dout] -- what `torch.gather(expert_outputs, idx)` gives the single-GPU competition step for its diversity
-        loss (an empty tensor otherwise); gradients of both are accepted.
-        `direct`: one message per (peer, local expert) straight into an expert-major buffer (exchange_direct) instead of one per peer
-        followed by a regroup pass (and its inverse before the return trip); same rows through the same kernels."""
-        x2 = x2.contiguous()
-        T = x2.shape[0]
-        bins = ops.bin_tokens(idx, E_global)
-        xs = ops.dispatch_tokens(x2, bins)
-        plan = make_plan(bins.counts, group, per_expert=direct)
-        El = plan.E_local
-        if direct:
-            rs = torch.empty(plan.R, xs.shape[1], dtype=xs.dtype, device=xs.device)
-            exchange_direct(direct_views(rs, plan, 0, El, True), direct_views(xs, plan, 0, El, False), group).wait()
-            lb = local_bins(plan, 0, El)
-        else:
-            recv = a2a_rows(xs, plan.send_splits, plan.recv_splits, group)
-            lb = ops.bin_tokens(local_expert_ids(plan).view(-1, 1), tab.E)
-            rs = ops.dispatch_rows(recv, lb)
-        hpre, hact = ops.grouped_gemm(rs, tab.w1_ptrs, tab.layout, tab.D, tab.F, lb.offsets, tab.E, bias_ptrs=tab.b1_ptrs,
-                                      epilogue=L.EPI_BIAS_ACT, act=tab.act, want_c2=True, want_c=tab.act != L.ACT_RELU)
-        ys = ops.grouped_gemm(hact, tab.w2_ptrs, tab.layout, tab.F, tab.Dout, lb.offsets, tab.E, bias_ptrs=tab.b2_ptrs,
-                              epilogue=L.EPI_BIAS if tab.b2_ptrs is not None else L.EPI_PLAIN)
-        if direct:
-            y = torch.empty(bins.n, ys.shape[1], dtype=ys.dtype, device=ys.device)
-            exchange_direct(direct_views(y, plan, 0, El, False), direct_views(ys, plan, 0, El, True), group).wait()
-        else:
-            y = a2a_rows(ops.dispatch_rows(ys, _Unsort(lb)), plan.recv_splits, plan.send_splits, group)
-        out = ops.combine(y, bins, idx, w, combine_mode, T)
-        ctx.direct = direct
-        ctx.saved = (bins, lb, plan, rs, hpre, hact, y)
-        ctx.tab, ctx.w, ctx.group, ctx.n_params = tab, w, group, len(params)
-        ctx.want_slots = want_slots
-        ctx.round_dw = combine_mode == L.COMBINE_SEQ_RW        # bf16 affinity weights: d w as autograd forms it (functional._ffn_backward)
-        y_tk = ops.dispatch_rows(y, _Unsort(bins)) if want_slots else y.new_empty(0)      # y_tk[t*K+k] = y[slot_of[t*K+k]]
-        return out, y_tk
-
-    @staticmethod
-    def backward(ctx, dout, dy_tk=None):
-        if ctx.saved is None:
-            raise RuntimeError("competesmoe_amd: saved activations were freed by the first backward pass; a second backward "
-                               "through the same graph (retain_graph=True) is not supported -- run the forward again")
-        bins, lb, plan, rs, hpre, hact, y = ctx.saved
-        ctx.saved = None
-        tab, group = ctx.tab, ctx.group
-        assert tab.layout == L.B_NK
-        E, dev, pd = tab.E, dout.device, tab.param_dtype
-        T = dout.shape[0]
-        dy, dw = ops.combine_bwd(dout.contiguous(), y, bins, ctx.w, want_dw=ctx.needs_input_grad[1], round_products=ctx.round_dw)
-        if dy_tk is not None and ctx.want_slots:               # gradient of the per-slot outputs (diversity loss), binned order
-            dy = dy + ops.dispatch_rows(dy_tk.contiguous(), ops.Bins(None, None, bins.perm, None, bins.n, bins.E, 1))
-        El = plan.E_local
-        if ctx.direct:
-            dys = torch.empty(plan.R, dy.shape[1], dtype=dy.dtype, device=dev)
-            exchange_direct(direct_views(dys, plan, 0, El, True), direct_views(dy, plan, 0, El, False), group).wait()
-        else:
-            dys = ops.dispatch_rows(a2a_rows(dy, plan.send_splits, plan.recv_splits, group), lb)
-        dh = ops.grouped_gemm(dys, tab.w2_ptrs, L.B_KN, tab.F, tab.F, lb.offsets, E, epilogue=L.EPI_ACTGRAD, act=tab.act,
-                              aux=hpre if hpre is not None else hact)
-        pg = [None] * ctx.n_params
-        if any(ctx.needs_input_grad[9:]):
-            es = torch.tensor([], dtype=pd).element_size()
-
-            def table(buf):
-                return ops.ptr_table(buf, E, buf[0].numel() * es)
-
-            gW2 = torch.empty(E, tab.Dout, tab.F, dtype=pd, device=dev)
-            ops.grouped_wgrad(dys, hact, lb.offsets, E, gW2, table(gW2), xcd_order=lb.xcd_order)
-            gW1 = torch.empty(E, tab.F, tab.D, dtype=pd, device=dev)
-            ops.grouped_wgrad(dh, rs, lb.offsets, E, gW1, table(gW1), xcd_order=lb.xcd_order)
-            seq = [gW1]
-            if tab.b1_ptrs is not None:
-                seq.append(_grouped_colsum(dh, lb.offsets, E, pd))      # rows cut into chunks when E * ceil(N / 512) would not fill the chip
-            seq.append(gW2)
-            if tab.b2_ptrs is not None:
-                seq.append(_grouped_colsum(dys, lb.offsets, E, pd))
-            pg = [g[e] for g in seq for e in range(E)]
-        dx2 = None
-        if ctx.needs_input_grad[0]:
-            dxs_s = ops.grouped_gemm(dh, tab.w1_ptrs, L.B_KN, tab.D, tab.D, lb.offsets, E)
-            if ctx.direct:
-                dxs = torch.empty(bins.n, dxs_s.shape[1], dtype=dxs_s.dtype, device=dev)
-                exchange_direct(direct_views(dxs, plan, 0, El, False), direct_views(dxs_s, plan, 0, El, True), group).wait()
-            else:
-                dxs = a2a_rows(ops.dispatch_rows(dxs_s, _Unsort(lb)), plan.recv_splits, plan.send_splits, group)
-            dx2 = ops.dispatch_rows_bwd(dxs, bins, T)
-        return (dx2, dw, None, None, None, None, None, None, None, *pg)
-
-
-class EPFFNChunked(torch.autograd.Function):
-    """EPFFN with the exchanges cut into groups of local experts and overlapped with the grouped GEMMs (module docstring).
-    Same numbers as EPFFN: every row goes through the same kernels with the same operands, only the launch grouping differs."""
-
-    @staticmethod
-    def forward(ctx, x2, w, idx, tab: ExpertTable, E_global: int, group, combine_mode: int, chunks: int, direct: bool, *params):
-        x2 = x2.contiguous()
-        T = x2.shape[0]
-        bins = ops.bin_tokens(idx, E_global)
-        xs = ops.dispatch_tokens(x2, bins)
-        plan = make_plan(bins.counts, group, per_expert=True)
-        cps = chunk_plan(plan, chunks)
-        recvs, works = [], []
-        for cp in cps:                                   # every outbound exchange is queued now, on the process group's stream
-            r = torch.empty(cp.R, xs.shape[1], dtype=xs.dtype, device=xs.device)
-            if direct:
-                works.append(exchange_direct(direct_views(r, plan, cp.e0, cp.e1, True), direct_views(xs, plan, cp.e0, cp.e1, False), group))
-            else:
-                works.append(exchange_views(_packed_views(r, cp.recv_n), _views(xs, cp.send_lo, cp.send_n), group))
-            recvs.append(r)
-        y = torch.empty(bins.n, tab.Dout, dtype=xs.dtype, device=xs.device)
-        back, keep, saved = [], [], []
-        for cp, r, wk in zip(cps, recvs, works):
-            with ops._timed("ep_wait_exposed"):
-                wk.wait()
-            Ec = cp.e1 - cp.e0
-            if direct or Ec == 1:       # one expert per group: rows grouped by source rank ARE expert-major, no regroup either way
-                lb, rs = local_bins(plan, cp.e0, cp.e1), r
-            else:
-                lb = ops.bin_tokens(local_expert_ids(plan, cp.e0, cp.e1).view(-1, 1), Ec)
-                rs = ops.dispatch_rows(r, lb)
-            hpre, hact = ops.grouped_gemm(rs, tab.w1_ptrs[cp.e0:cp.e1], tab.layout, tab.D, tab.F, lb.offsets, Ec,
-                                          bias_ptrs=None if tab.b1_ptrs is None else tab.b1_ptrs[cp.e0:cp.e1],
-                                          epilogue=L.EPI_BIAS_ACT, act=tab.act, want_c2=True, want_c=tab.act != L.ACT_RELU)
-            ys = ops.grouped_gemm(hact, tab.w2_ptrs[cp.e0:cp.e1], tab.layout, tab.F, tab.Dout, lb.offsets, Ec,
-                                  bias_ptrs=None if tab.b2_ptrs is None else tab.b2_ptrs[cp.e0:cp.e1],
-                                  epilogue=L.EPI_BIAS if tab.b2_ptrs is not None else L.EPI_PLAIN)
-            if direct:
-                ret = ys
-                back.append(exchange_direct(direct_views(y, plan, cp.e0, cp.e1, False), direct_views(ret, plan, cp.e0, cp.e1, True), group))
-            else:
-                ret = ys if Ec == 1 else ops.dispatch_rows(ys, _Unsort(lb))
-                back.append(exchange_views(_views(y, cp.send_lo, cp.send_n), _packed_views(ret, cp.recv_n), group))
-            keep.append(ret)                             # alive until the return trip has been waited for
-            saved.append((lb, rs, hpre, hact))
-        with ops._timed("ep_wait_exposed"):
-            for wk in back:
-                wk.wait()
-        del keep, recvs
-        out = ops.combine(y, bins, idx, w, combine_mode, T)
-        ctx.saved = (bins, plan, cps, saved, y)
-        ctx.tab, ctx.w, ctx.group, ctx.n_params = tab, w, group, len(params)
-        ctx.direct = direct
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        if ctx.saved is None:
-            raise RuntimeError("competesmoe_amd: saved activations were freed by the first backward pass; a second backward "
-                               "through the same graph (retain_graph=True) is not supported -- run the forward again")
-        bins, plan, cps, saved, y = ctx.saved
-        ctx.saved = None
-        tab, group = ctx.tab, ctx.group
-        assert tab.layout == L.B_NK
-        E, dev, pd = tab.E, dout.device, tab.param_dtype
-        T = dout.shape[0]
-        need_params = any(ctx.needs_input_grad[9:])
-        need_dx = ctx.needs_input_grad[0]
-        direct = ctx.direct
-        dy, dw = ops.combine_bwd(dout.contiguous(), y, bins, ctx.w, want_dw=ctx.needs_input_grad[1])
-        recvs, works = [], []
-        for cp in cps:
-            r = torch.empty(cp.R, dy.shape[1], dtype=dy.dtype, device=dev)
-            if direct:
-                works.append(exchange_direct(direct_views(r, plan, cp.e0, cp.e1, True), direct_views(dy, plan, cp.e0, cp.e1, False), group))
-            else:
-                works.append(exchange_views(_packed_views(r, cp.recv_n), _views(dy, cp.send_lo, cp.send_n), group))
-            recvs.append(r)
-        gW1 = gW2 = gb1 = gb2 = None
-        if need_params:
-            es = torch.tensor([], dtype=pd).element_size()
-
-            def table(buf):
-                return ops.ptr_table(buf, E, buf[0].numel() * es)
-
-            gW2 = torch.empty(E, tab.Dout, tab.F, dtype=pd, device=dev)
-            gW1 = torch.empty(E, tab.F, tab.D, dtype=pd, device=dev)
-            tW2, tW1 = table(gW2), table(gW1)
-            if tab.b1_ptrs is not None:
-                gb1 = torch.empty(E, tab.F, dtype=pd, device=dev)
-            if tab.b2_ptrs is not None:
-                gb2 = torch.empty(E, tab.Dout, dtype=pd, device=dev)
-        dxs = torch.empty(bins.n, tab.D, dtype=dy.dtype, device=dev) if need_dx else None
-        back, keep = [], []
-        for cp, r, wk, (lb, rs, hpre, hact) in zip(cps, recvs, works, saved):
-            with ops._timed("ep_wait_exposed"):
-                wk.wait()
-            e0, e1 = cp.e0, cp.e1
-            Ec = e1 - e0
-            dys = r if (direct or Ec == 1) else ops.dispatch_rows(r, lb)
-            dh = ops.grouped_gemm(dys, tab.w2_ptrs[e0:e1], L.B_KN, tab.F, tab.F, lb.offsets, Ec, epilogue=L.EPI_ACTGRAD, act=tab.act,
-                                  aux=hpre if hpre is not None else hact)
-            if need_dx:                                  # input gradient first: its return trip overlaps this group's weight gradients
-                dxs_s = ops.grouped_gemm(dh, tab.w1_ptrs[e0:e1], L.B_KN, tab.D, tab.D, lb.offsets, Ec)
-                if direct:
-                    ret = dxs_s
-                    back.append(exchange_direct(direct_views(dxs, plan, e0, e1, False), direct_views(ret, plan, e0, e1, True), group))
-                else:
-                    ret = dxs_s if Ec == 1 else ops.dispatch_rows(dxs_s, _Unsort(lb))
-                    back.append(exchange_views(_views(dxs, cp.send_lo, cp.send_n), _packed_views(ret, cp.recv_n), group))
-                keep.append(ret)
-            if need_params:
-                ops.grouped_wgrad(dys, hact, lb.offsets, Ec, gW2, tW2[e0:e1], xcd_order=lb.xcd_order)
-                ops.grouped_wgrad(dh, rs, lb.offsets, Ec, gW1, tW1[e0:e1], xcd_order=lb.xcd_order)
-                if gb1 is not None:         # a group's few experts: _grouped_colsum cuts their rows into chunks to fill the chip
-                    gb1[e0:e1] = _grouped_colsum(dh, lb.offsets, Ec, pd)
-                if gb2 is not None:
-                    gb2[e0:e1] = _grouped_colsum(dys, lb.offsets, Ec, pd)
-        pg = [None] * ctx.n_params
-        if need_params:
-            seq = [gW1] + ([gb1] if gb1 is not None else []) + [gW2] + ([gb2] if gb2 is not None else [])
-            pg = [g[e] for g in seq for e in range(E)]
-        dx2 = None
-        if need_dx:
-            with ops._timed("ep_wait_exposed"):
-                for wk in back:
-                    wk.wait()
-            del keep
-            dx2 = ops.dispatch_rows_bwd(dxs, bins, T)
-        return (dx2, dw, None, None, None, None, None, None, None, *pg)
-
-
-# ------------------------------------------------------------------------------------------------ packed experts (pretrain stack)
 class _Lane:
     """One group [e0, e1) of local experts of an exchange: carries rows of the token side's binned row space to their owners, where
     they stand expert-major, and rows back (per-peer messages + a regroup pass, or `direct`).  Narrow fp32 columns ([n, 1]: routing
@@ -515,6 +297,210 @@ class _Lane:
         return exchange_views(_views(dst, cp.send_lo, cp.send_n), _packed_views(rows, cp.recv_n), self.group), rows
 
 
+def _wait_all(back) -> None:
+    """Wait for every return trip queued with _Lane.give_back."""
+    with ops._timed("ep_wait_exposed"):
+        for wk, _ in back:
+            wk.wait()
+
+
+# ---- the owners' arithmetic of the LLaVA-stack functions: module experts [e0, e1) of `tab` on their expert-major rows
+def _local_ffn(tab: ExpertTable, e0: int, e1: int, rs: torch.Tensor, lb):
+    """GEMM 1 (+ b1, activation) and GEMM 2 (+ b2): (hpre, hact, ys)."""
+    hpre, hact = ops.grouped_gemm(rs, tab.w1_ptrs[e0:e1], tab.layout, tab.D, tab.F, lb.offsets, e1 - e0,
+                                  bias_ptrs=None if tab.b1_ptrs is None else tab.b1_ptrs[e0:e1],
+                                  epilogue=L.EPI_BIAS_ACT, act=tab.act, want_c2=True, want_c=tab.act != L.ACT_RELU)
+    ys = ops.grouped_gemm(hact, tab.w2_ptrs[e0:e1], tab.layout, tab.F, tab.Dout, lb.offsets, e1 - e0,
+                          bias_ptrs=None if tab.b2_ptrs is None else tab.b2_ptrs[e0:e1],
+                          epilogue=L.EPI_BIAS if tab.b2_ptrs is not None else L.EPI_PLAIN)
+    return hpre, hact, ys
+
+
+def _local_dh(tab: ExpertTable, e0: int, e1: int, dys, lb, hpre, hact):
+    """dH = dYs @ W2 through the activation gradient."""
+    return ops.grouped_gemm(dys, tab.w2_ptrs[e0:e1], L.B_KN, tab.F, tab.F, lb.offsets, e1 - e0, epilogue=L.EPI_ACTGRAD, act=tab.act,
+                            aux=hpre if hpre is not None else hact)
+
+
+def _local_dxs(tab: ExpertTable, e0: int, e1: int, dh, lb):
+    """dXs = dH @ W1.  Its own call: EPFFNChunked sends it home before the weight gradients, EPFFN forms them first."""
+    return ops.grouped_gemm(dh, tab.w1_ptrs[e0:e1], L.B_KN, tab.D, tab.D, lb.offsets, e1 - e0)
+
+
+def _wgrad_buffers(tab: ExpertTable, dev):
+    """(gW1 [E, F, D], its pointer table, gW2 [E, Dout, F], its pointer table) for all local experts."""
+    E, pd = tab.E, tab.param_dtype
+    es = torch.tensor([], dtype=pd).element_size()
+    gW2 = torch.empty(E, tab.Dout, tab.F, dtype=pd, device=dev)
+    gW1 = torch.empty(E, tab.F, tab.D, dtype=pd, device=dev)
+    tW2, tW1 = ops.ptr_table(gW2, E, gW2[0].numel() * es), ops.ptr_table(gW1, E, gW1[0].numel() * es)
+    return gW1, tW1, gW2, tW2
+
+
+def _local_wgrads(tab: ExpertTable, e0: int, e1: int, lb, rs, hact, dys, dh, bufs):
+    """Weight gradients of the experts [e0, e1) into their slices of `bufs` (_wgrad_buffers); returns their bias column sums
+    (gb1 [e1 - e0, F] | None, gb2 [e1 - e0, Dout] | None) -- _grouped_colsum cuts a few experts' rows into chunks to fill the chip."""
+    gW1, tW1, gW2, tW2 = bufs
+    Ec, pd = e1 - e0, tab.param_dtype
+    ops.grouped_wgrad(dys, hact, lb.offsets, Ec, gW2, tW2[e0:e1], xcd_order=lb.xcd_order)
+    ops.grouped_wgrad(dh, rs, lb.offsets, Ec, gW1, tW1[e0:e1], xcd_order=lb.xcd_order)
+    gb1 = _grouped_colsum(dh, lb.offsets, Ec, pd) if tab.b1_ptrs is not None else None
+    gb2 = _grouped_colsum(dys, lb.offsets, Ec, pd) if tab.b2_ptrs is not None else None
+    return gb1, gb2
+
+
+def _return_trip(rows, n: int, plan: EPPlan, lane, lb, group):
+    """EPFFN's blocking return trip of expert-major `rows` into a fresh [n, C] tensor in the token side's binned order."""
+    if lane is None:
+        return a2a_rows(ops.dispatch_rows(rows, _Unsort(lb)), plan.recv_splits, plan.send_splits, group)
+    dst = torch.empty(n, rows.shape[1], dtype=rows.dtype, device=rows.device)
+    lane.give_back(rows, dst)[0].wait()
+    return dst
+
+
+class EPFFN(torch.autograd.Function):
+    """dispatch -> all-to-all -> local grouped FFN -> all-to-all -> combine, and the mirrored backward."""
+
+    @staticmethod
+    def forward(ctx, x2, w, idx, tab: ExpertTable, E_global: int, group, combine_mode: int, want_slots: bool, direct: bool, *params):
+        """Returns (out [T, Dout], y_tk): the combined output and, with `want_slots`, the expert outputs per (token, k) slot in flat
+        order [T*K, Dout] -- what `torch.gather(expert_outputs, idx)` gives the single-GPU competition step for its diversity
+        loss (an empty tensor otherwise); gradients of both are accepted.
+        `direct`: one message per (peer, local expert) straight into an expert-major buffer -- ONE lane of all local experts, waited
+        for at once -- instead of one blocking all_to_all_single per trip followed by a regroup pass (and its inverse before the
+        return trip); same rows through the same kernels."""
+        x2 = x2.contiguous()
+        T = x2.shape[0]
+        bins = ops.bin_tokens(idx, E_global)
+        xs = ops.dispatch_tokens(x2, bins)
+        plan = make_plan(bins.counts, group, per_expert=direct)
+        lane = _Lane(plan, chunk_plan(plan, 1)[0], True, group) if direct else None
+        if direct:
+            r, wk = lane.send(xs)
+            wk.wait()
+            rs, lb = lane.arrived(r), lane.lb
+        else:
+            recv = a2a_rows(xs, plan.send_splits, plan.recv_splits, group)
+            lb = ops.bin_tokens(local_expert_ids(plan).view(-1, 1), tab.E)
+            rs = ops.dispatch_rows(recv, lb)
+        hpre, hact, ys = _local_ffn(tab, 0, tab.E, rs, lb)
+        y = _return_trip(ys, bins.n, plan, lane, lb, group)
+        out = ops.combine(y, bins, idx, w, combine_mode, T)
+        ctx.saved = (bins, lb, plan, lane, rs, hpre, hact, y)
+        ctx.tab, ctx.w, ctx.group, ctx.n_params = tab, w, group, len(params)
+        ctx.want_slots = want_slots
+        ctx.round_dw = combine_mode == L.COMBINE_SEQ_RW        # bf16 affinity weights: d w as autograd forms it (functional._ffn_backward)
+        y_tk = ops.dispatch_rows(y, _Unsort(bins)) if want_slots else y.new_empty(0)      # y_tk[t*K+k] = y[slot_of[t*K+k]]
+        return out, y_tk
+
+    @staticmethod
+    def backward(ctx, dout, dy_tk=None):
+        bins, lb, plan, lane, rs, hpre, hact, y = _take_saved(ctx)
+        tab, group = ctx.tab, ctx.group
+        assert tab.layout == L.B_NK
+        E, dev = tab.E, dout.device
+        T = dout.shape[0]
+        dy, dw = ops.combine_bwd(dout.contiguous(), y, bins, ctx.w, want_dw=ctx.needs_input_grad[1], round_products=ctx.round_dw)
+        if dy_tk is not None and ctx.want_slots:               # gradient of the per-slot outputs (diversity loss), binned order
+            dy = dy + ops.dispatch_rows(dy_tk.contiguous(), ops.Bins(None, None, bins.perm, None, bins.n, bins.E, 1))
+        if lane is None:
+            dys = ops.dispatch_rows(a2a_rows(dy, plan.send_splits, plan.recv_splits, group), lb)
+        else:
+            r, wk = lane.send(dy)
+            wk.wait()
+            dys = lane.arrived(r)
+        dh = _local_dh(tab, 0, E, dys, lb, hpre, hact)
+        grads = None
+        if any(ctx.needs_input_grad[9:]):
+            bufs = _wgrad_buffers(tab, dev)
+            gb1, gb2 = _local_wgrads(tab, 0, E, lb, rs, hact, dys, dh, bufs)
+            grads = (bufs[0], gb1, bufs[2], gb2)
+        dx2 = None
+        if ctx.needs_input_grad[0]:
+            dx2 = ops.dispatch_rows_bwd(_return_trip(_local_dxs(tab, 0, E, dh, lb), bins.n, plan, lane, lb, group), bins, T)
+        return (dx2, dw, None, None, None, None, None, None, None, *_module_grads(grads, E, ctx.n_params))
+
+
+class EPFFNChunked(torch.autograd.Function):
+    """EPFFN with the exchanges cut into groups of local experts -- one _Lane each -- and overlapped with the grouped GEMMs (module
+    docstring).  Same numbers as EPFFN: every row goes through the same kernels with the same operands, only the launch grouping
+    differs."""
+
+    @staticmethod
+    def forward(ctx, x2, w, idx, tab: ExpertTable, E_global: int, group, combine_mode: int, chunks: int, direct: bool, *params):
+        x2 = x2.contiguous()
+        T = x2.shape[0]
+        bins = ops.bin_tokens(idx, E_global)
+        xs = ops.dispatch_tokens(x2, bins)
+        plan = make_plan(bins.counts, group, per_expert=True)
+        lanes = [_Lane(plan, cp, direct, group) for cp in chunk_plan(plan, chunks)]
+        sent = [ln.send(xs) for ln in lanes]               # every outbound exchange is queued now, on the process group's stream
+        y = torch.empty(bins.n, tab.Dout, dtype=xs.dtype, device=xs.device)
+        back, saved = [], []
+        for ln, (r, wk) in zip(lanes, sent):
+            with ops._timed("ep_wait_exposed"):
+                wk.wait()
+            rs = ln.arrived(r)
+            hpre, hact, ys = _local_ffn(tab, ln.cp.e0, ln.cp.e1, rs, ln.lb)
+            back.append(ln.give_back(ys, y))
+            saved.append((rs, hpre, hact))
+        _wait_all(back)
+        del back, sent
+        out = ops.combine(y, bins, idx, w, combine_mode, T)
+        ctx.saved = (bins, lanes, saved, y)
+        ctx.tab, ctx.w, ctx.n_params = tab, w, len(params)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        bins, lanes, saved, y = _take_saved(ctx)
+        tab = ctx.tab
+        assert tab.layout == L.B_NK
+        E, dev, pd = tab.E, dout.device, tab.param_dtype
+        T = dout.shape[0]
+        need_params = any(ctx.needs_input_grad[9:])
+        need_dx = ctx.needs_input_grad[0]
+        dy, dw = ops.combine_bwd(dout.contiguous(), y, bins, ctx.w, want_dw=ctx.needs_input_grad[1])
+        sent = [ln.send(dy) for ln in lanes]
+        grads = None
+        if need_params:
+            bufs = _wgrad_buffers(tab, dev)
+            gb1 = torch.empty(E, tab.F, dtype=pd, device=dev) if tab.b1_ptrs is not None else None
+            gb2 = torch.empty(E, tab.Dout, dtype=pd, device=dev) if tab.b2_ptrs is not None else None
+            grads = (bufs[0], gb1, bufs[2], gb2)
+        dxs = torch.empty(bins.n, tab.D, dtype=dy.dtype, device=dev) if need_dx else None
+        back = []
+        for ln, (r, wk), (rs, hpre, hact) in zip(lanes, sent, saved):
+            with ops._timed("ep_wait_exposed"):
+                wk.wait()
+            e0, e1, lb = ln.cp.e0, ln.cp.e1, ln.lb
+            dys = ln.arrived(r)
+            dh = _local_dh(tab, e0, e1, dys, lb, hpre, hact)
+            if need_dx:                                  # input gradient first: its return trip overlaps this group's weight gradients
+                back.append(ln.give_back(_local_dxs(tab, e0, e1, dh, lb), dxs))
+            if need_params:
+                for buf, part in zip((gb1, gb2), _local_wgrads(tab, e0, e1, lb, rs, hact, dys, dh, bufs)):
+                    if buf is not None:
+                        buf[e0:e1] = part
+        dx2 = None
+        if need_dx:
+            _wait_all(back)
+            del back
+            dx2 = ops.dispatch_rows_bwd(dxs, bins, T)
+        return (dx2, dw, None, None, None, None, None, None, None, *_module_grads(grads, E, ctx.n_params))
+
+
+# ------------------------------------------------------------------------------------------------ packed experts (pretrain stack)
+def _packed_grad_buffers(El: int, D: int, F: int, Dout: int, pd, gb_dtype, dev):
+    """(gk [El, D, F], gv [El, F, Dout], their pointer tables, gb [El, F] in `gb_dtype` | None) of this rank's packed experts."""
+    es = torch.tensor([], dtype=pd).element_size()
+    gk = torch.empty(El, D, F, dtype=pd, device=dev)
+    gv = torch.empty(El, F, Dout, dtype=pd, device=dev)
+    tk, tv = ops.ptr_table(gk, El, D * F * es), ops.ptr_table(gv, El, F * Dout * es)
+    gb = None if gb_dtype is None else torch.empty(El, F, dtype=gb_dtype, device=dev)
+    return gk, gv, tk, tv, gb
+
+
 class EPFFNPacked(torch.autograd.Function):
     """functional.MoEFFNPacked (the pretrain stack's two `cvmm` calls, moe_pretrain_model/layers/moe/moe.py:397-435 + cvmm.py:490-551)
     with the packed experts sharded over the group: `keys` [E/P, D, F], `values` [E/P, F, Dout] (+ `bias` [E/P, F]) are THIS rank's
@@ -533,12 +519,11 @@ class EPFFNPacked(torch.autograd.Function):
         the deepseek layers (functional.DenseFFN's body), launched after every lane's send is queued and before the first wait, in the
         forward and in the backward; its output enters the combine epilogue as the residual (the bits of `out + out_shared`), its dx
         is returned as the gradient of `x_shared`, a separate input."""
-        from . import functional as Fn
         x2 = x2.contiguous()
         op = x2.dtype
         if op == torch.bfloat16:
             w = w.to(op).float()
-        El, D, F = keys.shape
+        _, D, F = keys.shape
         has_shared = x_shared is not None
         # the shared output takes the residual slot of the combine: no block residual may arrive with it (_fuses_residual = False)
         assert not (has_shared and residual is not None), "EPFFNPacked: a shared expert and a block residual share one combine slot"
@@ -567,22 +552,8 @@ class EPFFNPacked(torch.autograd.Function):
             v_op = torch.empty(values.shape, dtype=op, device=dev)
         else:
             k_op, v_op = operand(keys), operand(values)
-        es = k_op.element_size()
-        b_op = b1 = None
-        epi1 = L.EPI_BIAS_ACT
-        if bias is not None and bias.dtype == torch.float32 and op == torch.bfloat16:
-            b_op = bias.contiguous()
-            b1 = ops.ptr_table(b_op, El, F * 4)
-            epi1 = L.EPI_ROUND_BIAS32_ACT
-        elif bias is not None:
-            b_op = bias.contiguous() if bias.dtype == op else bias.to(op)
-            b1 = ops.ptr_table(b_op, El, F * es)
-        ob = None
-        if o_bias is not None:
-            ob = o_bias.contiguous() if o_bias.dtype == op else o_bias.to(op)
-        tab = ExpertTable(E=El, D=D, F=F, Dout=Dout, layout=L.B_KN, act=act, w1_ptrs=ops.ptr_table(k_op, El, D * F * es),
-                          w2_ptrs=ops.ptr_table(v_op, El, F * Dout * es), b1_ptrs=b1, b2_ptrs=None, param_dtype=keys.dtype, epi1=epi1,
-                          scale_after_gemm=combine_mode == L.COMBINE_DOT)
+        tab, b_op, ob = Fn._packed_table(k_op, v_op, bias, o_bias, act, combine_mode, keys.dtype)
+        b1, epi1 = tab.b1_ptrs, tab.epi1
         bins = ops.bin_tokens(idx, E_global)
         xs = ops.dispatch_tokens(x2, bins)
         plan = make_plan(bins.counts, group, per_expert=True)
@@ -616,9 +587,7 @@ class EPFFNPacked(torch.autograd.Function):
                 ys = ops.grouped_gemm(hact, tab.w2_ptrs[e0:e1], L.B_KN, Dout, Dout, lb.offsets, e1 - e0)
             back.append(ln.give_back(ys, y))
             saved.append((rs, hpre, hact))
-        with ops._timed("ep_wait_exposed"):
-            for wk, _ in back:
-                wk.wait()
+        _wait_all(back)
         del back, sent
         out = ops.combine(y, bins, idx, w, combine_mode, T, obias=ob, residual=None if residual is None else residual.contiguous())
         if stats is not None:               # `relu_pass_rate` over the rows this rank's experts processed
@@ -633,19 +602,14 @@ class EPFFNPacked(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        return EPFFNPacked._backward(ctx, dout)
+        return EPFFNPacked._backward(ctx, _take_saved(ctx), dout)
 
     @staticmethod
-    def _backward(ctx, dout, dy_extra=None):
+    def _backward(ctx, taken, dout, dy_extra=None):
         """`dy_extra`: gradient of the per-slot outputs (EPFFNPackedSlots) in binned order, operand dtype.  It travels to the owners as
         one more message per lane and enters there as functional._ffn_backward's `dy_extra` does: its own dH product (W2^T and the
         activation gradient, no routing weight) added to dH, and added to dy for d values; it carries no d w."""
-        from . import functional as Fn
-        if ctx.saved is None:
-            raise RuntimeError("competesmoe_amd: saved activations were freed by the first backward pass; a second backward "
-                               "through the same graph (retain_graph=True) is not supported -- run the forward again")
-        bins, lanes, saved, y = ctx.saved
-        ctx.saved = None
+        bins, lanes, saved, y = taken
         tab, op = ctx.tab, ctx.op
         El, D, F, Dout, pd = tab.E, tab.D, tab.F, tab.Dout, tab.param_dtype
         dev = dout.device
@@ -675,12 +639,7 @@ class EPFFNPacked(torch.autograd.Function):
             sh = (dx_s, gks, gvs, gbs)
         gk = gv = gb = None
         if need_params:
-            es = torch.tensor([], dtype=pd).element_size()
-            gk = torch.empty(El, D, F, dtype=pd, device=dev)
-            gv = torch.empty(El, F, Dout, dtype=pd, device=dev)
-            tk, tv = ops.ptr_table(gk, El, D * F * es), ops.ptr_table(gv, El, F * Dout * es)
-            if tab.b1_ptrs is not None:
-                gb = torch.empty(El, F, dtype=pd, device=dev)
+            gk, gv, tk, tv, gb = _packed_grad_buffers(El, D, F, Dout, pd, pd if tab.b1_ptrs is not None else None, dev)
         dxs = torch.empty(bins.n, D, dtype=op, device=dev) if need_dx else None
         dots = torch.empty(bins.n, 1, dtype=torch.float32, device=dev) if use_dot else None
         back = []
@@ -735,9 +694,7 @@ class EPFFNPacked(torch.autograd.Function):
                 ops.grouped_wgrad(rs, dh, lb.offsets, Ec, gk, tk[e0:e1], xcd_order=lb.xcd_order)
                 if gb is not None:
                     gb[e0:e1] = _grouped_colsum(dh, lb.offsets, Ec, pd)
-        with ops._timed("ep_wait_exposed"):
-            for wk, _ in back:
-                wk.wait()
+        _wait_all(back)
         del back, sent
         if use_dot:
             dw = dots.view(-1)[bins.slot_of.long()].view(T, bins.K)
@@ -764,11 +721,7 @@ class EPFFNPackedFP8(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x2, w, idx, keys, values, bias, act: int, combine_mode: int, E_global: int, group, chunks: int, direct: bool,
                 cache: bool = False, x_shared=None, keys_shared=None, values_shared=None, bias_shared=None):
-        from . import functional as Fn
-        x2 = x2.contiguous()
-        if x2.dtype != torch.bfloat16:
-            raise ValueError("competesmoe_amd: the fp8 expert path takes bf16 activations (run under bf16 autocast)")
-        w = w.to(torch.bfloat16).float()          # the K weights enter as bf16 values; d w comes back unrounded
+        x2, w = Fn._fp8_rows_and_weights(x2, w)
         El, D, F = keys.shape
         Dout = values.shape[2]
         T = x2.shape[0]
@@ -785,10 +738,7 @@ class EPFFNPackedFP8(torch.autograd.Function):
             ctx.shared = (sh_saved, sh_cfg)
         (kq_b, ks_b), (kq, ks) = Fn._quantize_weight_both(keys, cache)        # backward pair [El, D, F]; forward pair [El, F, D]
         (vq_b, vs_b), (vq, vs) = Fn._quantize_weight_both(values, cache)      # backward pair [El, F, Dout]; forward pair [El, Dout, F]
-        b_op = b1 = None
-        if bias is not None:
-            b_op = bias.to(torch.bfloat16).contiguous()
-            b1 = ops.ptr_table(b_op, El, F * 2)
+        b_op, b1 = Fn._fp8_bias_table(bias)
         y = torch.empty(bins.n, Dout, dtype=torch.bfloat16, device=dev)
         back, saved = [], []
         for ln, (r, wk) in zip(lanes, sent):
@@ -804,9 +754,7 @@ class EPFFNPackedFP8(torch.autograd.Function):
             ys = ops.grouped_gemm_mxfp8(hq, hs, vq[e0:e1], vs[e0:e1], lb.offsets)
             back.append(ln.give_back(ys, y))
             saved.append((rs, hpre, hact))
-        with ops._timed("ep_wait_exposed"):
-            for wk, _ in back:
-                wk.wait()
+        _wait_all(back)
         del back, sent
         out = ops.combine(y, bins, idx, w, combine_mode, T, residual=y_shared)
         ctx.saved = (bins, lanes, saved, y, b_op)
@@ -817,14 +765,9 @@ class EPFFNPackedFP8(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        from . import functional as Fn
-        if ctx.saved is None:
-            raise RuntimeError("competesmoe_amd: saved activations were freed by the first backward pass; run the forward again")
-        bins, lanes, saved, y, _ = ctx.saved
-        ctx.saved = None
+        bins, lanes, saved, y, _ = _take_saved(ctx)
         act, bias_dtype = ctx.cfg
         El, D, F, Dout = ctx.shape
-        pd = ctx.pd
         dev = dout.device
         T = dout.shape[0]
         need = ctx.needs_input_grad
@@ -844,12 +787,7 @@ class EPFFNPackedFP8(torch.autograd.Function):
         ctx.wq = None
         gk = gv = gb = None
         if need_params:
-            es = torch.tensor([], dtype=pd).element_size()
-            gk = torch.empty(El, D, F, dtype=pd, device=dev)
-            gv = torch.empty(El, F, Dout, dtype=pd, device=dev)
-            tk, tv = ops.ptr_table(gk, El, D * F * es), ops.ptr_table(gv, El, F * Dout * es)
-            if bias_dtype is not None:
-                gb = torch.empty(El, F, dtype=bias_dtype, device=dev)
+            gk, gv, tk, tv, gb = _packed_grad_buffers(El, D, F, Dout, ctx.pd, bias_dtype, dev)
         dxs = torch.empty(bins.n, D, dtype=torch.bfloat16, device=dev) if need_dx else None
         back = []
         for ln, (r, wk), (rs, hpre, hact) in zip(lanes, sent, saved):
@@ -870,9 +808,7 @@ class EPFFNPackedFP8(torch.autograd.Function):
                 ops.grouped_wgrad(rs, dh, lb.offsets, Ec, gk, tk[e0:e1], xcd_order=lb.xcd_order)
                 if gb is not None:
                     gb[e0:e1] = _grouped_colsum(dh, lb.offsets, Ec, bias_dtype)
-        with ops._timed("ep_wait_exposed"):
-            for wk, _ in back:
-                wk.wait()
+        _wait_all(back)
         del back, sent
         dx2 = ops.dispatch_rows_bwd(dxs, bins, T) if need_dx else None
         return (dx2, dw, None, gk, gv, gb, None, None, None, None, None, None, None, *sh)
@@ -893,7 +829,6 @@ class EPFFNPackedSlots(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x2, w, idx, keys, values, bias, o_bias, act: int, combine_mode: int, E_global: int, group, chunks: int,
                 direct: bool, residual=None, stats=None):
-        from .functional import _SlotMap
         out = EPFFNPacked.forward(ctx, x2, w, idx, keys, values, bias, o_bias, act, combine_mode, E_global, group, chunks, direct,
                                   residual, stats)
         bins, y = ctx.saved[0], ctx.saved[3]
@@ -902,16 +837,14 @@ class EPFFNPackedSlots(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, dy_tk):
-        from .functional import _SlotMap
-        if ctx.saved is None:
-            return EPFFNPacked._backward(ctx, dout)       # raises the second-backward error
-        bins = ctx.saved[0]
+        taken = _take_saved(ctx)
+        bins = taken[0]
         extra = None
         if dy_tk is not None:                             # binned order, in the operand dtype: one more message per lane
             extra = ops.dispatch_rows(dy_tk.reshape(bins.n, -1).to(ctx.op).contiguous(), _SlotMap(bins.perm, bins.n))
         if dout is None:
             dout = torch.zeros(ctx.w.shape[0], ctx.tab.Dout, dtype=ctx.op, device=ctx.w.device)
-        return EPFFNPacked._backward(ctx, dout, extra)[:15]     # this function takes no shared expert
+        return EPFFNPacked._backward(ctx, taken, dout, extra)[:15]     # this function takes no shared expert
 
 
 # default of the local competition pass's dX chain, read once per process: 1 = every expert after the first adds its dX product into the
@@ -926,12 +859,10 @@ class LocalCompetitionAffinity(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xa, keys, values, act: int, fp32_affinity: bool):
-        from .functional import CompetitionAffinityPacked
         return CompetitionAffinityPacked.forward(ctx, xa, keys, values, act, fp32_affinity)
 
     @staticmethod
     def backward(ctx, daff):
-        from .functional import CompetitionAffinityPacked
         return CompetitionAffinityPacked._backward(ctx, daff, _COMP_DX_ACCUM)
 
 
@@ -939,7 +870,6 @@ def local_competition_affinity(xa: torch.Tensor, keys: torch.Tensor, values: tor
     """Affinities [P*T, El] of the gathered rows to this rank's experts.  Where the affinity epilogues cannot run (ops.affinity_ok:
     fp32 operands, odd sizes) each local expert is a DenseFFN over the gathered rows followed by SoftplusMean -- the stored form of
     the single-GPU pass; only the affinities are kept, the selected outputs come from the sparse step either way."""
-    from .functional import DenseFFN, SoftplusMean
     if ops.affinity_ok(xa, keys.shape[2], values.shape[2]):
         return LocalCompetitionAffinity.apply(xa, keys, values, act, fp32_affinity)
     return torch.stack([SoftplusMean.apply(DenseFFN.apply(xa, keys[e], None, values[e], None, act, L.B_KN), fp32_affinity)
@@ -1108,7 +1038,6 @@ class EPCompeteSMoE(MoeLayer):
 
     def competition_policy(self, x):
         """[T, E] affinities of the local tokens to ALL experts, then the single-GPU selection (competesmoe.py:219-259)."""
-        from .functional import RouterSelect, SoftplusMean
         B, N, D = x.shape
         xa = AllGatherRows.apply(x.reshape(B * N, D), self.group)                   # [P*T, D]
         outs = [self.dense_expert(i, xa.view(1, -1, D)) for i in range(len(self.experts))]

@@ -9,7 +9,7 @@ import os
 import threading
 import weakref
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import Optional
 
 import torch
 
@@ -594,16 +594,30 @@ def _take_handoff():
     return h
 
 
+def _take_saved(ctx):
+    """`ctx.saved`, handed over once: the first backward pass through a node releases its activations."""
+    saved, ctx.saved = ctx.saved, None
+    if saved is None:
+        raise RuntimeError("competesmoe_amd: the MoE layer's saved activations were freed by the first backward pass "
+                           "(they are released early to bound memory); a second backward through the same graph "
+                           "(retain_graph=True) is not supported -- run the forward again")
+    return saved
+
+
+def _module_grads(grads, E: int, n_params: int) -> list:
+    """Per-module gradient list in the order of the `params` a module-expert function was applied to: W1, [b1], W2, [b2], each
+    E entries.  `grads` = (gW1, gb1 | None, gW2, gb2 | None) as [E, ...] tensors, or None."""
+    if grads is None:
+        return [None] * n_params
+    return [g[e] for g in grads if g is not None for e in range(E)]
+
+
 def _ffn_backward(dout, w, tab: ExpertTable, saved, need_dx: bool, need_dw: bool, need_params: bool, dy_extra=None, dx_add=None,
                   handoff=None):
     """Returns dx2, dw, (gW1 [E,..], gb1 [E,F]|None, gW2 [E,..], gb2 [E,Dout]|None).
     `dx_add`: a callable dw -> [T, D] tensor (or None) added to dx INSIDE the gather-sum of the binned rows (csmoe_dispatch_rows_bwd's
     `add` input): the gate-path gradient of x, which depends on this function's dw (SparseMoEModules).
     `handoff`: DxHandoff of a shared-expert layer (its always-on expert's dx becomes the chain's first addend)."""
-    if saved is None:
-        raise RuntimeError("competesmoe_amd: the MoE layer's saved activations were freed by the first backward pass "
-                           "(they are released early to bound memory); a second backward through the same graph "
-                           "(retain_graph=True) is not supported -- run the forward again")
     bins, xs, hpre, hact, y, *rest = saved
     # competition steps hand in bf16 routing weights (COMBINE_SEQ_RW): the reference's `weights * out_exp` is then a bf16 product and
     # its autograd forms d w = (grad * out).sum(-1) with every product rounded to bf16 and the sum rounded once (moe.py:204)
@@ -716,16 +730,9 @@ class MoEFFNModules(_ForwardAware):
     def backward(ctx, dout):
         tab = ctx.tab
         need_params = any(ctx.needs_input_grad[5:])
-        dx2, dw, grads = _ffn_backward(dout, ctx.w, tab, ctx.saved, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+        dx2, dw, grads = _ffn_backward(dout, ctx.w, tab, _take_saved(ctx), ctx.needs_input_grad[0], ctx.needs_input_grad[1],
                                        need_params, handoff=ctx.handoff)
-        ctx.saved = None
-        pg: List[Optional[torch.Tensor]] = [None] * ctx.n_params
-        if grads is not None:
-            gW1, gb1, gW2, gb2 = grads
-            E = tab.E
-            seq = [gW1] + ([gb1] if gb1 is not None else []) + [gW2] + ([gb2] if gb2 is not None else [])
-            pg = [g[e] for g in seq for e in range(E)]
-        return (dx2, dw, None, None, None, *pg)
+        return (dx2, dw, None, None, None, *_module_grads(grads, tab.E, ctx.n_params))
 
 
 class SparseMoEModules(_ForwardAware):
@@ -785,20 +792,14 @@ class SparseMoEModules(_ForwardAware):
             grads = None
         else:
             want_dw = need_x or need_wg          # d w only matters through the gate
-            dx2, dw, grads = _ffn_backward(dout, w, tab, ctx.saved, need_x, want_dw, need_params, dx_add=gate_path if need_x else None)
-            ctx.saved = None
+            dx2, dw, grads = _ffn_backward(dout, w, tab, _take_saved(ctx), need_x, want_dw, need_params,
+                                           dx_add=gate_path if need_x else None)
             if not need_x:
                 gate_path(dw)
         dwg = None
         if need_wg and box.get("ds") is not None:
             dwg = _gate_wgrad(box["ds"], x2, ctx.w_dtype, small)
-        pg: List[Optional[torch.Tensor]] = [None] * ctx.n_params
-        if grads is not None:
-            gW1, gb1, gW2, gb2 = grads
-            E = tab.E
-            seq = [gW1] + ([gb1] if gb1 is not None else []) + [gW2] + ([gb2] if gb2 is not None else [])
-            pg = [g[e] for g in seq for e in range(E)]
-        return (dx2, dwg, None, None, None, None, None, *pg)
+        return (dx2, dwg, None, None, None, None, None, *_module_grads(grads, tab.E, ctx.n_params))
 
 
 class _SlotMap:
@@ -826,25 +827,17 @@ class MoEFFNModulesSlots(_ForwardAware):
     @staticmethod
     def backward(ctx, dout, dy_tk):
         tab = ctx.tab
-        if ctx.saved is None:
-            _ffn_backward(dout, ctx.w, tab, None, False, False, False)        # raises the second-backward error
-        bins = ctx.saved[0]
+        saved = _take_saved(ctx)
+        bins = saved[0]
         extra = None
         if dy_tk is not None:
             extra = ops.dispatch_rows(dy_tk.reshape(bins.n, -1).contiguous(), _SlotMap(bins.perm, bins.n))   # binned row m <- slot perm[m]
         if dout is None:
-            dout = torch.zeros(ctx.w.shape[0], tab.Dout, dtype=ctx.saved[4].dtype, device=ctx.w.device)
+            dout = torch.zeros(ctx.w.shape[0], tab.Dout, dtype=saved[4].dtype, device=ctx.w.device)
         need_params = any(ctx.needs_input_grad[5:])
-        dx2, dw, grads = _ffn_backward(dout, ctx.w, tab, ctx.saved, ctx.needs_input_grad[0], ctx.needs_input_grad[1], need_params,
+        dx2, dw, grads = _ffn_backward(dout, ctx.w, tab, saved, ctx.needs_input_grad[0], ctx.needs_input_grad[1], need_params,
                                        dy_extra=extra)
-        ctx.saved = None
-        pg: List[Optional[torch.Tensor]] = [None] * ctx.n_params
-        if grads is not None:
-            gW1, gb1, gW2, gb2 = grads
-            E = tab.E
-            seq = [gW1] + ([gb1] if gb1 is not None else []) + [gW2] + ([gb2] if gb2 is not None else [])
-            pg = [g[e] for g in seq for e in range(E)]
-        return (dx2, dw, None, None, None, *pg)
+        return (dx2, dw, None, None, None, *_module_grads(grads, tab.E, ctx.n_params))
 
 
 class MoEFFNModulesResidual(_ForwardAware):
@@ -865,16 +858,37 @@ class MoEFFNModulesResidual(_ForwardAware):
     def backward(ctx, dout):
         tab = ctx.tab
         need_params = any(ctx.needs_input_grad[6:])
-        dx2, dw, grads = _ffn_backward(dout, ctx.w, tab, ctx.saved, ctx.needs_input_grad[0], ctx.needs_input_grad[2],
+        dx2, dw, grads = _ffn_backward(dout, ctx.w, tab, _take_saved(ctx), ctx.needs_input_grad[0], ctx.needs_input_grad[2],
                                        need_params)
-        ctx.saved = None
-        pg: List[Optional[torch.Tensor]] = [None] * ctx.n_params
-        if grads is not None:
-            gW1, gb1, gW2, gb2 = grads
-            E = tab.E
-            seq = [gW1] + ([gb1] if gb1 is not None else []) + [gW2] + ([gb2] if gb2 is not None else [])
-            pg = [g[e] for g in seq for e in range(E)]
-        return (dx2, dout if ctx.needs_input_grad[1] else None, dw, None, None, None, *pg)
+        return (dx2, dout if ctx.needs_input_grad[1] else None, dw, None, None, None, *_module_grads(grads, tab.E, ctx.n_params))
+
+
+def _packed_table(k_op, v_op, bias, o_bias, act: int, combine_mode: int, param_dtype):
+    """(tab, b_op, ob) of packed experts from their operand-dtype copies `k_op` [E, D, F] / `v_op` [E, F, Dout] (written or not:
+    only their addresses are taken) and the master `bias` / `o_bias`: ExpertTable, and the bias / output bias the kernels read."""
+    op = k_op.dtype
+    E, D, F = k_op.shape
+    Dout = v_op.shape[2]
+    es = k_op.element_size()
+    b_op = None
+    b1 = None
+    epi1 = L.EPI_BIAS_ACT
+    if bias is not None and bias.dtype == torch.float32 and op == torch.bfloat16:
+        # `scores = cvmm(...) + self.bias[sel]` under autocast (moe.py:400-405): the fp32 master bias is added to the ALREADY
+        # ROUNDED bf16 product in fp32, the activation sees that sum, the next cvmm rounds it
+        b_op = bias.contiguous()
+        b1 = ops.ptr_table(b_op, E, F * 4)
+        epi1 = L.EPI_ROUND_BIAS32_ACT
+    elif bias is not None:
+        b_op = bias.contiguous() if bias.dtype == op else bias.to(op)
+        b1 = ops.ptr_table(b_op, E, F * es)
+    ob = None
+    if o_bias is not None:
+        ob = o_bias.contiguous() if o_bias.dtype == op else o_bias.to(op)
+    tab = ExpertTable(E=E, D=D, F=F, Dout=Dout, layout=L.B_KN, act=act,
+                      w1_ptrs=ops.ptr_table(k_op, E, D * F * es), w2_ptrs=ops.ptr_table(v_op, E, F * Dout * es),
+                      b1_ptrs=b1, b2_ptrs=None, param_dtype=param_dtype, epi1=epi1, scale_after_gemm=combine_mode == L.COMBINE_DOT)
+    return tab, b_op, ob
 
 
 class MoEFFNPacked(_ForwardAware):
@@ -894,7 +908,7 @@ class MoEFFNPacked(_ForwardAware):
             # sits inside the reference's autograd function -- the gradient it returns for the fp32 weights is not rounded.  (Casting
             # outside, `w.to(bf16).float()`, makes autograd round d w to bf16 on the way back: 1.6e-3 off, tools/grad_stage_probe.py.)
             w = w.to(op).float()
-        E, D, F = keys.shape
+        _, D, F = keys.shape
         Dout = values.shape[2]
         dev = x2.device
         k_hit = v_hit = False
@@ -936,25 +950,7 @@ class MoEFFNPacked(_ForwardAware):
             v_op = values.to(op)
         if _WEIGHT_CACHE_ON and not v_hit and values.dtype != op:
             _remember(values, op, v_op)
-        es = k_op.element_size()
-        b_op = None
-        b1 = None
-        epi1 = L.EPI_BIAS_ACT
-        if bias is not None and bias.dtype == torch.float32 and op == torch.bfloat16:
-            # `scores = cvmm(...) + self.bias[sel]` under autocast (moe.py:400-405): the fp32 master bias is added to the ALREADY
-            # ROUNDED bf16 product in fp32, the activation sees that sum, the next cvmm rounds it
-            b_op = bias.contiguous()
-            b1 = ops.ptr_table(b_op, E, F * 4)
-            epi1 = L.EPI_ROUND_BIAS32_ACT
-        elif bias is not None:
-            b_op = bias.contiguous() if bias.dtype == op else bias.to(op)
-            b1 = ops.ptr_table(b_op, E, F * es)
-        ob = None
-        if o_bias is not None:
-            ob = o_bias.contiguous() if o_bias.dtype == op else o_bias.to(op)
-        tab = ExpertTable(E=E, D=D, F=F, Dout=Dout, layout=L.B_KN, act=act,
-                          w1_ptrs=ops.ptr_table(k_op, E, D * F * es), w2_ptrs=ops.ptr_table(v_op, E, F * Dout * es),
-                          b1_ptrs=b1, b2_ptrs=None, param_dtype=keys.dtype, epi1=epi1, scale_after_gemm=combine_mode == L.COMBINE_DOT)
+        tab, b_op, ob = _packed_table(k_op, v_op, bias, o_bias, act, combine_mode, keys.dtype)
         out, saved = _ffn_forward(x2, w, idx, tab, combine_mode, ob, residual=None if residual is None else residual.contiguous(),
                                   before_gemm2=side, masters=masters,
                                   # the decode path reads bf16 operands that exist already: bf16 parameters, or the operand cache's
@@ -971,13 +967,12 @@ class MoEFFNPacked(_ForwardAware):
         return out
 
     @staticmethod
-    def _backward(ctx, dout, dy_extra=None):
+    def _backward(ctx, saved, dout, dy_extra=None):
         """(dx2, dw, gk, gv, gb, gob) -- shared with MoEFFNPackedSlots, whose per-slot output gradient arrives as `dy_extra`."""
         tab = ctx.tab
         need_params = ctx.needs_input_grad[3] or ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
-        dx2, dw, grads = _ffn_backward(dout, ctx.w, tab, ctx.saved, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+        dx2, dw, grads = _ffn_backward(dout, ctx.w, tab, saved, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
                                        need_params, dy_extra=dy_extra)
-        ctx.saved = None
         gk = gv = gb = gob = None
         if grads is not None:
             gk, gb1, gv, _ = grads
@@ -989,7 +984,7 @@ class MoEFFNPacked(_ForwardAware):
 
     @staticmethod
     def backward(ctx, dout):
-        dx2, dw, gk, gv, gb, gob = MoEFFNPacked._backward(ctx, dout)
+        dx2, dw, gk, gv, gb, gob = MoEFFNPacked._backward(ctx, _take_saved(ctx), dout)
         return dx2, dw, None, gk, gv, gb, gob, None, None, (dout if (ctx.has_residual and ctx.needs_input_grad[9]) else None), None
 
 
@@ -1007,15 +1002,14 @@ class MoEFFNPackedSlots(_ForwardAware):
 
     @staticmethod
     def backward(ctx, dout, dy_tk):
-        if ctx.saved is None:
-            _ffn_backward(dout, ctx.w, ctx.tab, None, False, False, False)    # raises the second-backward error
-        bins = ctx.saved[0]
+        saved = _take_saved(ctx)
+        bins = saved[0]
         extra = None
         if dy_tk is not None:
             extra = ops.dispatch_rows(dy_tk.reshape(bins.n, -1).contiguous(), _SlotMap(bins.perm, bins.n))
         if dout is None:
-            dout = torch.zeros(ctx.w.shape[0], ctx.tab.Dout, dtype=ctx.saved[4].dtype, device=ctx.w.device)
-        dx2, dw, gk, gv, gb, gob = MoEFFNPacked._backward(ctx, dout, extra)
+            dout = torch.zeros(ctx.w.shape[0], ctx.tab.Dout, dtype=saved[4].dtype, device=ctx.w.device)
+        dx2, dw, gk, gv, gb, gob = MoEFFNPacked._backward(ctx, saved, dout, extra)
         return dx2, dw, None, gk, gv, gb, gob, None, None
 
 
@@ -1405,6 +1399,23 @@ def _ffn_fp8_decode(x2, w1, w2, b1, act: int, offsets, src_rows, src_div: int):
     return ops.grouped_gemm_skinny_mxfp8(hq, hs, vq, vs, offsets)
 
 
+def _fp8_rows_and_weights(x2, w):
+    """Checked inputs of the fp8 expert functions: contiguous bf16 rows, and the K weights as bf16 VALUES in fp32 (as in MoEFFNPacked;
+    d w comes back unrounded)."""
+    x2 = x2.contiguous()
+    if x2.dtype != torch.bfloat16:
+        raise ValueError("competesmoe_amd: the fp8 expert path takes bf16 activations (run under bf16 autocast)")
+    return x2, w.to(torch.bfloat16).float()
+
+
+def _fp8_bias_table(bias):
+    """(bf16 copy of the packed `bias` [E, F], its pointer table), or (None, None)."""
+    if bias is None:
+        return None, None
+    b_op = bias.to(torch.bfloat16).contiguous()
+    return b_op, ops.ptr_table(b_op, bias.shape[0], bias.shape[1] * 2)
+
+
 class MoEFFNPackedFP8(_ForwardAware):
     """MoEFFNPacked with the four row-space expert GEMMs of a step (GEMM 1, GEMM 2, dH, dXs) on the block-scaled fp8 matrix pipe
     (BASELINE config 5; `csmoe_grouped_gemm_mxfp8`): operands quantised to MXFP8 (e4m3 + one e8m0 scale per 32 elements along each
@@ -1418,10 +1429,7 @@ class MoEFFNPackedFP8(_ForwardAware):
 
     @staticmethod
     def forward(ctx, x2, w, idx, keys, values, bias, act: int, combine_mode: int, cache: bool = False, wgrad_fp8: bool = False):
-        x2 = x2.contiguous()
-        if x2.dtype != torch.bfloat16:
-            raise ValueError("competesmoe_amd: the fp8 expert path takes bf16 activations (run under bf16 autocast)")
-        w = w.to(torch.bfloat16).float()          # the K weights enter as bf16 values (as in MoEFFNPacked); d w comes back unrounded
+        x2, w = _fp8_rows_and_weights(x2, w)
         E, D, F = keys.shape
         T = x2.shape[0]
         bins = ops.bin_tokens(idx, E)
@@ -1432,10 +1440,7 @@ class MoEFFNPackedFP8(_ForwardAware):
             return ops.combine(y, bins, idx, w, combine_mode, T)
         xs, xq, xsc = ops.dispatch_tokens_mxfp8(x2, bins)       # the gather and the quantiser in one pass (CSMOE_DISPATCH_QUANT=0: two)
         (kq_b, ks_b), (kq, ks) = _quantize_weight_both(keys, cache)        # backward pair [E, D, F]; forward pair [E, F, D] (reduction over D)
-        b_op = b1 = None
-        if bias is not None:
-            b_op = bias.to(torch.bfloat16).contiguous()
-            b1 = ops.ptr_table(b_op, E, F * 2)
+        b_op, b1 = _fp8_bias_table(bias)
         hpre, hact = ops.grouped_gemm_mxfp8(xq, xsc, kq, ks, bins.offsets, bias_ptrs=b1, epilogue=L.EPI_BIAS_ACT, act=act,
                                             want_c2=True, want_c=act != L.ACT_RELU)
         del xq, xsc, kq, ks
@@ -1452,10 +1457,7 @@ class MoEFFNPackedFP8(_ForwardAware):
 
     @staticmethod
     def backward(ctx, dout):
-        if ctx.saved is None:
-            raise RuntimeError("competesmoe_amd: saved activations were freed by the first backward pass; run the forward again")
-        bins, xs, hpre, hact, y, _ = ctx.saved
-        ctx.saved = None
+        bins, xs, hpre, hact, y, _ = _take_saved(ctx)
         act, bias_dtype = ctx.cfg
         keys, values = ctx.keys, ctx.values
         E, D, F = keys.shape

@@ -31,6 +31,33 @@ def _experts(E, D, F, seed, dt, dev):
     return ex.to(dev).to(dt)
 
 
+def _gloo_shims(ep):
+    """Several ranks on ONE device: RCCL refuses, so for these tests the collectives are carried by gloo through host memory
+    (`all_to_all_single`, `all_gather`, and the (peer, expert) messages of `exchange_direct`)."""
+    real_a2a, real_ag, real_direct = dist.all_to_all_single, dist.all_gather, ep.exchange_direct
+
+    def a2a_host(out, inp, output_split_sizes=None, input_split_sizes=None, group=None):
+        o = torch.empty(out.shape, dtype=out.dtype)
+        real_a2a(o, inp.cpu(), output_split_sizes=output_split_sizes, input_split_sizes=input_split_sizes, group=group)
+        out.copy_(o)
+
+    def ag_host(outs, inp, group=None):
+        hs = [torch.empty(o.shape, dtype=o.dtype) for o in outs]
+        real_ag(hs, inp.cpu(), group=group)
+        for o, h in zip(outs, hs):
+            o.copy_(h)
+
+    def direct_host(dst, src, group=None):
+        src_h = [(p_, v.cpu()) for p_, v in src]
+        dst_h = [(p_, torch.empty(v.shape, dtype=v.dtype)) for p_, v in dst]
+        real_direct(dst_h, src_h, group).wait()
+        for (_, d_), (_, h_) in zip(dst, dst_h):
+            if d_.shape[0]:
+                d_.copy_(h_)
+        return ep._Works([])
+    dist.all_to_all_single, dist.all_gather, ep.exchange_direct = a2a_host, ag_host, direct_host
+
+
 def _run(rank, world, port, backend, dt_name, q, chunks=1, empty_half=False):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -41,24 +68,7 @@ def _run(rank, world, port, backend, dt_name, q, chunks=1, empty_half=False):
         from competesmoe_amd import ep
         from competesmoe_amd.moe import get_moe
         if backend == "gloo":
-            real = dist.all_to_all_single
-
-            def via_host(out, inp, output_split_sizes=None, input_split_sizes=None, group=None):
-                o = torch.empty(out.shape, dtype=out.dtype)
-                real(o, inp.cpu(), output_split_sizes=output_split_sizes, input_split_sizes=input_split_sizes, group=group)
-                out.copy_(o)
-            dist.all_to_all_single = via_host
-            real_direct = ep.exchange_direct
-
-            def direct_via_host(dst, src, group=None):       # gloo moves host tensors: stage the (peer, expert) messages through the host
-                src_h = [(p_, v.cpu()) for p_, v in src]
-                dst_h = [(p_, torch.empty(v.shape, dtype=v.dtype)) for p_, v in dst]
-                real_direct(dst_h, src_h, group).wait()
-                for (_, d_), (_, h_) in zip(dst, dst_h):
-                    if d_.shape[0]:
-                        d_.copy_(h_)
-                return ep._Works([])
-            ep.exchange_direct = direct_via_host
+            _gloo_shims(ep)
         dt = torch.float32 if dt_name == "fp32" else torch.bfloat16
         B, N, D, F, E, K = 2, 96, 64, 128, 8, 2
         args = types.SimpleNamespace(balance_loss_coef=0.01, router_z_loss_coef=0.001)
@@ -123,20 +133,8 @@ def _run_comp(rank, world, port, backend, dt_name, q, *unused):
     try:
         from competesmoe_amd import ep
         from competesmoe_amd.moe import get_moe
-        if backend == "gloo":          # two ranks on ONE device: RCCL refuses, the collectives go through host memory for this test
-            real_a2a, real_ag = dist.all_to_all_single, dist.all_gather
-
-            def a2a_host(out, inp, output_split_sizes=None, input_split_sizes=None, group=None):
-                o = torch.empty(out.shape, dtype=out.dtype)
-                real_a2a(o, inp.cpu(), output_split_sizes=output_split_sizes, input_split_sizes=input_split_sizes, group=group)
-                out.copy_(o)
-
-            def ag_host(outs, inp, group=None):
-                hs = [torch.empty(o.shape, dtype=o.dtype) for o in outs]
-                real_ag(hs, inp.cpu(), group=group)
-                for o, h in zip(outs, hs):
-                    o.copy_(h)
-            dist.all_to_all_single, dist.all_gather = a2a_host, ag_host
+        if backend == "gloo":
+            _gloo_shims(ep)
         dt = torch.float32 if dt_name == "fp32" else torch.bfloat16
         B, N, D, F, E, K = 2, 64, 64, 128, 8, 2
         args = types.SimpleNamespace(balance_loss_coef=0.01, router_z_loss_coef=0.001, rate_flip=1.0, warm_up=0.0, max_compete_in_iter=8,
@@ -202,24 +200,7 @@ def _run_pretrain(rank, world, port, backend, dt_name, q, chunks=1, empty_half=F
         from competesmoe_amd import ep
         from competesmoe_amd.pretrain import get_moe
         if backend == "gloo":
-            real = dist.all_to_all_single
-
-            def via_host(out, inp, output_split_sizes=None, input_split_sizes=None, group=None):
-                o = torch.empty(out.shape, dtype=out.dtype)
-                real(o, inp.cpu(), output_split_sizes=output_split_sizes, input_split_sizes=input_split_sizes, group=group)
-                out.copy_(o)
-            dist.all_to_all_single = via_host
-            real_direct = ep.exchange_direct
-
-            def direct_via_host(dst, src, group=None):
-                src_h = [(p_, v.cpu()) for p_, v in src]
-                dst_h = [(p_, torch.empty(v.shape, dtype=v.dtype)) for p_, v in dst]
-                real_direct(dst_h, src_h, group).wait()
-                for (_, d_), (_, h_) in zip(dst, dst_h):
-                    if d_.shape[0]:
-                        d_.copy_(h_)
-                return ep._Works([])
-            ep.exchange_direct = direct_via_host
+            _gloo_shims(ep)
         bias = dt_name.endswith("_bias")
         block = dt_name.endswith("_block")     # inside pretrain.MoEBlock: fp32 stream, fused LayerNorm + gate, residual in the combine
         autocast = dt_name.startswith("bf16")
@@ -327,11 +308,16 @@ def test_ep_world2_one_gpu_equals_single_gpu(dt_name):
     assert _launch(2, "gloo", dt_name) == {0: True, 1: True}
 
 
-@pytest.mark.parametrize("world,backend,dt_name", [(1, "nccl", "fp32"), (1, "nccl", "bf16"), (2, "gloo", "fp32")])
-def test_competesmoe_ep_equals_single_gpu(world, backend, dt_name):
+@pytest.mark.parametrize("world,backend,dt_name,direct",
+                         [pytest.param(1, "nccl", "fp32", False, id="1-nccl-fp32"), pytest.param(1, "nccl", "bf16", False, id="1-nccl-bf16"),
+                          pytest.param(2, "gloo", "fp32", False, id="2-gloo-fp32"), pytest.param(1, "nccl", "bf16", True, id="1-nccl-bf16-direct"),
+                          pytest.param(2, "gloo", "fp32", True, id="2-gloo-fp32-direct")])
+def test_competesmoe_ep_equals_single_gpu(world, backend, dt_name, direct, monkeypatch):
     """`competesmoe_ep`: a competition step (gather tokens, dense local experts, scatter affinities, sparse recompute through the
     exchange, diversity loss on the exchanged rows) and a router step give the single-GPU `competesmoe` layer's outputs bit for bit
-    and its losses / gradients within accumulation-order noise."""
+    and its losses / gradients within accumulation-order noise -- per-peer and (CSMOE_EP_DIRECT=1) on the direct road, the only
+    runs of EPFFN's direct branch with per-slot outputs."""
+    monkeypatch.setenv("CSMOE_EP_DIRECT", "1" if direct else "0")
     assert _launch(world, backend, dt_name, target=_run_comp) == {r: True for r in range(world)}
 
 
