@@ -37,6 +37,37 @@ void csmoe_set_error(const char* fmt, ...);
     }                                                                                \
   } while (0)
 
+// Raise kernel Kern's dynamic-LDS limit to Bytes, once.  One flag per kernel instantiation: keyed on the kernel itself, not on its
+// function-pointer type (which every instantiation shares, so a `static bool` in a function template on that type was set by the
+// first launch of any of them)
+template <auto Kern, int Bytes>
+int set_dyn_lds() {
+  static bool done = false;
+  if (!done) {
+    hipError_t e = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, Bytes);
+    if (e != hipSuccess) { csmoe_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return CSMOE_ERR_LAUNCH; }
+    done = true;
+  }
+  return CSMOE_OK;
+}
+
+// Grid of a 1-D launch of `tiles` workgroups: *grid = 0 with CSMOE_OK when there is nothing to launch, a refusal past 2^31 - 1.
+//   unsigned grid;  if ((rc = grid_1d("name", tiles, &grid)) || !grid) return rc;
+inline int grid_1d(const char* name, int64_t tiles, unsigned* grid) {
+  *grid = 0;
+  if (tiles <= 0) return CSMOE_OK;
+  if (tiles > 0x7fffffff) { csmoe_set_error("%s: grid too large", name); return CSMOE_ERR_UNSUPPORTED; }
+  *grid = (unsigned)tiles;
+  return CSMOE_OK;
+}
+// upper bound of the tiles of a row-space launch (the counts stay on the device): every expert may end in one partial row tile
+inline int64_t rowspace_tiles(int M, int E, int N, int BMt, int BNt) {
+  return (int64_t)((N + BNt - 1) / BNt) * ((M + BMt - 1) / BMt + E);
+}
+
+// upper bound of the 16-row blocks of a decode launch: sum_e ceil(count_e / 16) <= min(M, M / 16 + E) whatever the counts are
+inline int64_t skinny_row_blocks(int M, int E) { return M < (int64_t)M / 16 + E ? M : (int64_t)M / 16 + E; }
+
 // grid-stride row kernels: 4 rows (waves) per workgroup; caps of 2048..16384 workgroups measure the same (tools/hbm_bench.py)
 inline int stride_grid(int rows) {
   const int g = (rows + 3) / 4;

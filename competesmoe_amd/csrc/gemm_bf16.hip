@@ -253,19 +253,6 @@ __global__ void __launch_bounds__(256, 2) gg_fast_kernel(FastArgs p) {
   }
 }
 
-// one flag per kernel instantiation: keyed on the kernel itself, not on its function-pointer type (which every instantiation
-// shares, so a `static bool` inside a function template on that type was set by the first launch of any of them)
-template <auto Kern>
-int set_lds() {
-  static bool done = false;
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) { csmoe_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return CSMOE_ERR_LAUNCH; }
-    done = true;
-  }
-  return CSMOE_OK;
-}
-
 }  // namespace
 
 bool gg_fast_rowspace_ok(int64_t lda, int64_t ldb, int64_t ldc, int M, int N, int Kd, const void* A, const void* C) {
@@ -280,21 +267,16 @@ int gg_fast_rowspace(const void* A, int64_t lda, const void* const* b_ptrs, int 
                      const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2,
                      const void* aux, int64_t ldc, int epilogue, int act, const void* single_B, const void* single_bias,
                      hipStream_t st) {
-  FastArgs p{};
-  p.single_M = M; p.single_B = single_B; p.single_bias = single_bias;
-  p.R = A; p.ld_r = lda; p.c_ptrs_in = b_ptrs; p.ld_c = ldb; p.bias_ptrs = bias_ptrs; p.offsets = offsets; p.E = E;
-  p.NC = N; p.Kd = Kd; p.C = C; p.C2 = C2; p.aux = aux; p.ldc = ldc; p.epilogue = epilogue; p.act = act;
-  int nct = (N + BN - 1) / BN;
-  int64_t grid = (int64_t)nct * ((M + BM - 1) / BM + E);
-  if (grid <= 0) return CSMOE_OK;
-  if (grid > 0x7fffffff) { csmoe_set_error("grouped_gemm: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
-  int rc;
+  const FastArgs p = rowspace_args(A, lda, b_ptrs, ldb, bias_ptrs, offsets, E, M, N, Kd, C, C2, aux, ldc, epilogue, act, single_B, single_bias);
+  unsigned grid;
+  int rc = grid_1d("grouped_gemm", rowspace_tiles(M, E, N, BM, BN), &grid);
+  if (rc || !grid) return rc;
   if (b_layout == CSMOE_B_NK) {
-    if ((rc = set_lds<gg_fast_kernel<KC, KC, 0>>())) return rc;
-    hipLaunchKernelGGL((gg_fast_kernel<KC, KC, 0>), dim3((unsigned)grid), dim3(256), LDS_BYTES, st, p);
+    if ((rc = set_dyn_lds<gg_fast_kernel<KC, KC, 0>, LDS_BYTES>())) return rc;
+    hipLaunchKernelGGL((gg_fast_kernel<KC, KC, 0>), dim3(grid), dim3(256), LDS_BYTES, st, p);
   } else {
-    if ((rc = set_lds<gg_fast_kernel<KC, KM, 0>>())) return rc;
-    hipLaunchKernelGGL((gg_fast_kernel<KC, KM, 0>), dim3((unsigned)grid), dim3(256), LDS_BYTES, st, p);
+    if ((rc = set_dyn_lds<gg_fast_kernel<KC, KM, 0>, LDS_BYTES>())) return rc;
+    hipLaunchKernelGGL((gg_fast_kernel<KC, KM, 0>), dim3(grid), dim3(256), LDS_BYTES, st, p);
   }
   CSMOE_CHECK_LAUNCH("grouped_gemm(bf16)");
   return CSMOE_OK;
@@ -318,7 +300,7 @@ int gg_fast_wgrad(const void* A, int64_t lda, const void* B, int64_t ldb, const 
   if (grid <= 0) return CSMOE_OK;
   if (grid > 0x7fffffff) { csmoe_set_error("grouped_wgrad: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
   int rc;
-  if ((rc = set_lds<gg_fast_kernel<KM, KM, 1>>())) return rc;
+  if ((rc = set_dyn_lds<gg_fast_kernel<KM, KM, 1>, LDS_BYTES>())) return rc;
   hipLaunchKernelGGL((gg_fast_kernel<KM, KM, 1>), dim3((unsigned)grid), dim3(256), LDS_BYTES, st, p);
   CSMOE_CHECK_LAUNCH("grouped_wgrad(bf16)");
   return CSMOE_OK;

@@ -44,7 +44,6 @@ using namespace ggt;
 namespace {
 
 constexpr int BM2 = 256, BN2 = 256, BK2 = 64;
-constexpr int CT2_LD = BN2 + 4;              // fp32 epilogue staging row stride (floats); 128 rows per pass
 constexpr int LDS2_BYTES = EPI_LDS_BYTES;   // 135,168 B: the epilogue's bf16 staging tile (>= the 8 operand images = 131,072 B)
 
 enum { WIDE = 2, BAL = 3 };
@@ -60,7 +59,7 @@ __device__ unsigned long long* g_stamp_buf = nullptr;
 #define RT_STAMP(var) do { } while (0)
 #endif
 
-template <int ROWK, int COLK, int MODE, int SCHED, bool ACC = false>   // ACC: the CSMOE_EPI_ACCUM epilogue only (rowspace_epilogue)
+template <int ROWK, int COLK, int SCHED, bool ACC = false>   // ACC: the CSMOE_EPI_ACCUM epilogue only (rowspace_epilogue)
 __global__ void __launch_bounds__(512, 2) gg8_kernel(FastArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   RT_STAMP(st_entry);
@@ -69,34 +68,10 @@ __global__ void __launch_bounds__(512, 2) gg8_kernel(FastArgs p) {
   const int wm = wave >> 2, wn = wave & 3;       // row half, column quarter
 
   // ---------------- tile lookup ----------------
-  int e, row0 = 0, rows = 0, tr0 = 0, tc0 = 0, red_len;
   const int nct = (p.NC + BN2 - 1) / BN2;
-  if (MODE == 0) {
-    TilePos tp;
-    const int total = grouped_total_tiles(p.offsets, p.E, p.single_M, BM2, nct, lane, p.row_part);
-    if ((int)blockIdx.x >= total) return;
-    const int v = xcd_remap(blockIdx.x, total);
-    if (!grouped_find_tile(p.offsets, p.E, p.single_M, BM2, nct, v, lane, tp, p.row_part)) return;
-    e = tp.e;
-    row0 = tp.o0 + tp.mt * BM2; rows = min(BM2, tp.o1 - row0);
-    tc0 = tp.nt * BN2;
-    red_len = p.Kd;
-  } else {
-    const int nrt = (p.NR + BM2 - 1) / BM2;
-    const int per_e = nrt * nct;
-    int v = xcd_remap(blockIdx.x, per_e * p.E);
-    e = v / per_e;
-    int local = v - e * per_e;
-    tr0 = (local / nct) * BM2; tc0 = (local % nct) * BN2;
-    row0 = p.offsets ? p.offsets[e] : 0;
-    red_len = (p.offsets ? p.offsets[e + 1] : p.single_M) - row0;
-  }
-  e = __builtin_amdgcn_readfirstlane(e);
-  row0 = __builtin_amdgcn_readfirstlane(row0);
-  rows = __builtin_amdgcn_readfirstlane(rows);
-  tr0 = __builtin_amdgcn_readfirstlane(tr0);
-  tc0 = __builtin_amdgcn_readfirstlane(tc0);
-  red_len = __builtin_amdgcn_readfirstlane(red_len);
+  FIND_TILE_OR_RETURN(tp, p.offsets, p.E, p.single_M, BM2, nct, 0, p.row_part);
+  TILE_VARS_8W(tp, BM2, BN2);
+  const int red_len = p.Kd;
 
   // ---------------- operand descriptors + per-lane DMA offsets of the 4 image kinds ----------------
   const unsigned ldr_b = (unsigned)p.ld_r * 2u, ldc_b = (unsigned)p.ld_c * 2u;
@@ -106,7 +81,7 @@ __global__ void __launch_bounds__(512, 2) gg8_kernel(FastArgs p) {
   // RL / RH = tile rows [0,128) / [128,256); CL / CH = tile columns [0,128) / [128,256): contiguous, fully coalesced images.
   // Wave (wm, wn) owns rows {wm*64 + 0..63} of BOTH row images and columns {wn*32 + 0..31} of BOTH column images, i.e. four
   // 64x32 blocks of the 256x256 tile, so every image is consumed in exactly one phase by all eight waves.
-  if (MODE == 0) {
+  {
 #ifdef CSMOE_SAME_TILE   // diagnostic: every tile reads the operands of tile (expert 0, rows 0.., columns 0..): the loop with all fetches L2 hits
     rs_r = make_rsrc((const char*)p.R, (unsigned)rows * ldr_b);
 #else
@@ -131,64 +106,32 @@ __global__ void __launch_bounds__(512, 2) gg8_kernel(FastArgs p) {
       dma_setup<KM, 2>(vb_cl, ax_c, ldc_b, tc0_rd, p.NC, 7, 0, 0, wave, lane);
       dma_setup<KM, 2>(vb_ch, ax_dummy, ldc_b, tc0_rd, p.NC, 7, 0, 128, wave, lane);
     }
-  } else {
-    rs_r = make_rsrc((const char*)p.R + (int64_t)row0 * ldr_b, (unsigned)red_len * ldr_b);
-    dma_setup<KM, 2>(vb_rl, ax_r, ldr_b, tr0, p.NR, 7, 0, 0, wave, lane);
-    dma_setup<KM, 2>(vb_rh, ax_dummy, ldr_b, tr0, p.NR, 7, 0, 128, wave, lane);
-    rs_c = make_rsrc((const char*)p.Cflat + (int64_t)row0 * ldc_b, (unsigned)red_len * ldc_b);
-    dma_setup<KM, 2>(vb_cl, ax_c, ldc_b, tc0, p.NC, 7, 0, 0, wave, lane);
-    dma_setup<KM, 2>(vb_ch, ax_dummy, ldc_b, tc0, p.NC, 7, 0, 128, wave, lane);
   }
 
   // ---------------- LDS read addressing ----------------
-  const int g = lane >> 4, i16 = lane & 15;
-  const int kc_lane = i16 * 128 + ((g ^ (i16 >> 1)) << 4);
-  const int q = i16 >> 2, pp = i16 & 3;
-  const int fk = q | ((g & 1) << 2);
   // this wave's 16-row / 16-column blocks inside an image: R images blocks wm*4 + 0..3, C images blocks wn*2 + 0..1
-  const int r_blk0 = wm * 4, c_blk0 = wn * 2;
-  int km_r[4], km_c[2];
-#pragma unroll
-  for (int b = 0; b < 4; ++b) km_r[b] = (8 * g + q) * 256 + (((r_blk0 + b) ^ fk) << 5) + pp * 8;
-#pragma unroll
-  for (int b = 0; b < 2; ++b) km_c[b] = (8 * g + q) * 256 + (((c_blk0 + b) ^ fk) << 5) + pp * 8;
+  FRAG_LANE_8W(wm, wn);
+  FRAG_KM_BLOCKS(km_r, 4, r_blk0);
+  FRAG_KM_BLOCKS(km_c, 2, c_blk0);
 
   RT_STAMP(st_setup);
-  f32x4 acc[4][8];   // [column block][row block]
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  ZERO_ACC(acc, 4, 8);   // [column block][row block]
 
   const int nk = (red_len + BK2 - 1) / BK2;
 
-  // slot(kind, parity) = (parity * 4 + kind) * 16 KiB with kind RL=0, CL=1, CH=2, RH=3
-#define SLOT(kind, tile) (smem + ((((tile) & 1) * 4 + (kind)) * TILE_B))
+  // SLOT, WAIT_DMA, PHASE_SYNC_IN / _OUT: gemm_tiles.h
 #define ISSUE_RL(tile) dma_tile<ROWK, 2>(rs_r, SLOT(0, tile), vb_rl, ax_r, (tile) * BK2, red_len, ldr_b, wave)
 #define ISSUE_CL(tile) dma_tile<COLK, 2>(rs_c, SLOT(1, tile), vb_cl, ax_c, (tile) * BK2, red_len, ldc_b, wave)
 #define ISSUE_CH(tile) dma_tile<COLK, 2>(rs_c, SLOT(2, tile), vb_ch, ax_c, (tile) * BK2, red_len, ldc_b, wave)
 #define ISSUE_RH(tile) dma_tile<ROWK, 2>(rs_r, SLOT(3, tile), vb_rh, ax_r, (tile) * BK2, red_len, ldr_b, wave)
-#define WAIT_DMA(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-  // barrier A closes a phase's read/issue section (reads retired, counted DMA wait taken), barrier B its MFMA section
-#define PHASE_SYNC_IN()                                \
-  __builtin_amdgcn_sched_barrier(0);                   \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-  __builtin_amdgcn_s_barrier();                        \
-  __builtin_amdgcn_sched_barrier(0);                   \
-  __builtin_amdgcn_s_setprio(1)
-  // epilogue barrier: LDS traffic only (__syncthreads() adds s_waitcnt vmcnt(0): a wait for the pass's own global stores)
-#define EPI_SYNC()                                     \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-  __builtin_amdgcn_s_barrier();                        \
-  asm volatile("" ::: "memory")
-#define PHASE_SYNC_OUT()                               \
-  __builtin_amdgcn_s_setprio(0);                       \
-  __builtin_amdgcn_sched_barrier(0);                   \
-  __builtin_amdgcn_s_barrier();                        \
-  __builtin_amdgcn_sched_barrier(0)
+  // fragment reads of the thin and the BAL loop: block cb / rb of an image over both K-steps -> fc[cb] / fc[2 + cb] / fr[rb]
+#define READ2_CL(cb) _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) fc[cb][ks] = (COLK == KC) ? frag_kc(i_cl, kc_lane, c_blk0 + cb, ks) : frag_km_raw(i_cl, km_c[cb], ks);
+#define READ2_CH(cb) _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) fc[2 + cb][ks] = (COLK == KC) ? frag_kc(i_ch, kc_lane, c_blk0 + cb, ks) : frag_km_raw(i_ch, km_c[cb], ks);
+#define READ2_RL(rb) _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) fr[rb][ks] = (ROWK == KC) ? frag_kc(i_rl, kc_lane, r_blk0 + rb, ks) : frag_km_raw(i_rl, km_r[rb], ks);
+#define READ2_RH(rb) _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) fr[rb][ks] = (ROWK == KC) ? frag_kc(i_rh, kc_lane, r_blk0 + rb, ks) : frag_km_raw(i_rh, km_r[rb], ks);
   // ragged tiles: a wave whose 64-row / 32-column strips lie outside the tile skips those reads and MFMAs (it still issues
   // its share of the DMA and takes every barrier)
-  const int rows_here = (MODE == 0 ? rows : min(BM2, p.NR - tr0)) - wm * 64;
+  const int rows_here = rows - wm * 64;
   const int cols_here = min(BN2, p.NC - tc0) - wn * 32;
 
   // Tiles of at most 128 rows (the remainder tile of an expert: with ~1024 +- 32 rows per expert every other expert has one of
@@ -196,16 +139,16 @@ __global__ void __launch_bounds__(512, 2) gg8_kernel(FastArgs p) {
   // wave) and two barriers instead of four.  In the full-tile loops such a tile ran 70-83 % as long as a 256-row tile
   // (tools/tile_stamps.py: the loop is paced by the DMA issue and the barriers, not by the MFMAs it skips); CSMOE_THIN_LOOP=0
   // sends them through the full-tile loop again (A/B).
-  if (MODE == 0 && rows <= 128 && p.thin_loop) {
+  if (rows <= 128 && p.thin_loop) {
     const bool rlo = rows_here > 0, clo = cols_here > 0, chi = cols_here > 128;
     ISSUE_CL(0); ISSUE_CH(0); ISSUE_RL(0); ISSUE_CL(1); ISSUE_CH(1); ISSUE_RL(1);
     WAIT_DMA(6);                                           // K-tile 0 landed
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 #define THIN_FRAG_DECL bf16x8 fc[4][2], fr[4][2];
-#define THIN_READ_CL(cb) _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) fc[cb][ks] = (COLK == KC) ? frag_kc(i_cl, kc_lane, c_blk0 + cb, ks) : frag_km_raw(i_cl, km_c[cb], ks);
-#define THIN_READ_CH(cb) _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) fc[2 + cb][ks] = (COLK == KC) ? frag_kc(i_ch, kc_lane, c_blk0 + cb, ks) : frag_km_raw(i_ch, km_c[cb], ks);
-#define THIN_READ_RL(rb) _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) fr[rb][ks] = (ROWK == KC) ? frag_kc(i_rl, kc_lane, r_blk0 + rb, ks) : frag_km_raw(i_rl, km_r[rb], ks);
+#define THIN_READ_CL(cb) READ2_CL(cb)
+#define THIN_READ_CH(cb) READ2_CH(cb)
+#define THIN_READ_RL(rb) READ2_RL(rb)
 #define THIN_KSTEPS 2
 #define THIN_MFMA(ks, cb, rb) acc[cb][rb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fc[cb][ks], fr[rb][ks], acc[cb][rb], 0, 0, 0);
 #define THIN_ISSUE(s) ISSUE_CL(s + 2); ISSUE_CH(s + 2); ISSUE_RL(s + 2)
@@ -231,10 +174,10 @@ __global__ void __launch_bounds__(512, 2) gg8_kernel(FastArgs p) {
     if (wm == 1) __builtin_amdgcn_s_barrier();             // row half 1 starts half a phase late
     __builtin_amdgcn_sched_barrier(0);
 #define BAL_FRAG_DECL bf16x8 fc[4][2], fr[4][2];
-#define BAL_READ_CL(cb) _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) fc[cb][ks] = (COLK == KC) ? frag_kc(i_cl, kc_lane, c_blk0 + cb, ks) : frag_km_raw(i_cl, km_c[cb], ks);
-#define BAL_READ_CH(cb) _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) fc[2 + cb][ks] = (COLK == KC) ? frag_kc(i_ch, kc_lane, c_blk0 + cb, ks) : frag_km_raw(i_ch, km_c[cb], ks);
-#define BAL_READ_RL(rb) _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) fr[rb][ks] = (ROWK == KC) ? frag_kc(i_rl, kc_lane, r_blk0 + rb, ks) : frag_km_raw(i_rl, km_r[rb], ks);
-#define BAL_READ_RH(rb) _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) fr[rb][ks] = (ROWK == KC) ? frag_kc(i_rh, kc_lane, r_blk0 + rb, ks) : frag_km_raw(i_rh, km_r[rb], ks);
+#define BAL_READ_CL(cb) READ2_CL(cb)
+#define BAL_READ_CH(cb) READ2_CH(cb)
+#define BAL_READ_RL(rb) READ2_RL(rb)
+#define BAL_READ_RH(rb) READ2_RH(rb)
 #define BAL_PHASE_A_EXTRA
 #define BAL_KSTEPS 2
 #define BAL_MFMA(ks, cb, rb, arb) acc[cb][arb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fc[cb][ks], fr[rb][ks], acc[cb][arb], 0, 0, 0);
@@ -275,58 +218,10 @@ __global__ void __launch_bounds__(512, 2) gg8_kernel(FastArgs p) {
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
 
-  // ---------------- epilogue: two passes of 128 rows through an fp32 LDS tile ----------------
-  // ---------------- epilogue ----------------
-  if constexpr (MODE == 0) {
-    const EpiArgs ea{p.C, p.C2, p.aux, p.bias_ptrs ? p.bias_ptrs[e] : p.single_bias, p.ldc, p.epilogue, p.act, p.NC};
-    if constexpr (ACC) epi_run<EC_ACCUM, 0>(ea, acc, smem, row0, rows, tc0, wm, wn, lane);
-    else rowspace_epilogue(ea, acc, smem, row0, rows, tc0, wm, wn, lane);
-  } else {
-    // weight-gradient form (kept for the MODE = 1 instantiation; the launched weight-gradient kernel is gemm_bf16_v2p.hip's):
-    // two passes of 128 rows through an fp32 LDS tile
-    float* stg = (float*)smem;
-    const int ec = (threadIdx.x & 31) * 8, er = threadIdx.x >> 5;
-    const int ncol = tc0 + ec;
-#pragma unroll 1
-    for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb) {
-          const int m = wm * 64 + rb * 16 + i16;
-          const int n = (cb >> 1) * 128 + wn * 32 + (cb & 1) * 16 + 4 * g;
-          *(f32x4*)(stg + m * CT2_LD + n) = pass == 0 ? acc[cb][rb] : acc[cb][4 + rb];
-        }
-      EPI_SYNC();
-      if (ncol < p.NC) {
-      char* Ce = (char*)(p.out_ptrs ? p.out_ptrs[e] : p.single_C);
-      const int rlim = min(128, p.NR - tr0 - pass * 128);
-#pragma unroll 1
-      for (int r = er; r < rlim; r += 16) {
-        f32x4 lo = *(const f32x4*)(stg + r * CT2_LD + ec), hi = *(const f32x4*)(stg + r * CT2_LD + ec + 4);
-        const int64_t o = (int64_t)(tr0 + pass * 128 + r) * p.ldc + ncol;
-        if (p.out_f32) {
-          f32x4* dst = (f32x4*)(Ce + o * 4);
-          if (p.accumulate) { lo += dst[0]; hi += dst[1]; }
-          dst[0] = lo; dst[1] = hi;
-        } else {
-          bf16x8* dst = (bf16x8*)(Ce + o * 2);
-          float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          if (p.accumulate) {
-            const bf16x8 old = *dst;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] += (float)old[j];
-          }
-          bf16x8 o8;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) o8[j] = (bf16)v[j];
-          *dst = o8;
-        }
-      }
-      }
-      EPI_SYNC();
-    }
-  }
+  // ---------------- epilogue (gemm_epilogue.h) ----------------
+  const EpiArgs ea{p.C, p.C2, p.aux, p.bias_ptrs ? p.bias_ptrs[e] : p.single_bias, p.ldc, p.epilogue, p.act, p.NC};
+  if constexpr (ACC) epi_run<EC_ACCUM, 0>(ea, acc, smem, row0, rows, tc0, wm, wn, lane);
+  else rowspace_epilogue(ea, acc, smem, row0, rows, tc0, wm, wn, lane);
 #ifdef CSMOE_STAMPS
   if (threadIdx.x == 0 && g_stamp_buf) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the tile's own stores have left the wave
@@ -353,38 +248,21 @@ int sched_pref(int b_layout) {
   return b_layout == CSMOE_B_NK ? BAL : WIDE;
 }
 
-// one flag per kernel instantiation (keyed on the kernel, not on the function-pointer type all instantiations share)
-template <auto Kern>
-int set_lds2() {
-  static bool done = false;
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2_BYTES);
-    if (e != hipSuccess) { csmoe_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return CSMOE_ERR_LAUNCH; }
-    done = true;
-  }
-  return CSMOE_OK;
-}
-
 }  // namespace
 
 static int rowspace_launch(const void* A, int64_t lda, const void* const* b_ptrs, int b_layout, int64_t ldb,
                            const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2,
                            const void* aux, int64_t ldc, int epilogue, int act, const void* single_B, const void* single_bias,
                            hipStream_t st, int row_part) {
-  FastArgs p{};
+  FastArgs p = rowspace_args(A, lda, b_ptrs, ldb, bias_ptrs, offsets, E, M, N, Kd, C, C2, aux, ldc, epilogue, act, single_B, single_bias);
   p.row_part = row_part;
-  p.single_M = M; p.single_B = single_B; p.single_bias = single_bias;
-  p.R = A; p.ld_r = lda; p.c_ptrs_in = b_ptrs; p.ld_c = ldb; p.bias_ptrs = bias_ptrs; p.offsets = offsets; p.E = E;
-  p.NC = N; p.Kd = Kd; p.C = C; p.C2 = C2; p.aux = aux; p.ldc = ldc; p.epilogue = epilogue; p.act = act;
   {
     static const int thin = [] { const char* e = getenv("CSMOE_THIN_LOOP"); return e ? atoi(e) : 1; }();
     p.thin_loop = thin;
   }
-  int nct = (N + BN2 - 1) / BN2;
-  int64_t grid = (int64_t)nct * ((M + BM2 - 1) / BM2 + E);
-  if (grid <= 0) return CSMOE_OK;
-  if (grid > 0x7fffffff) { csmoe_set_error("grouped_gemm: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
-  int rc;
+  unsigned grid;
+  int rc = grid_1d("grouped_gemm", rowspace_tiles(M, E, N, BM2, BN2), &grid);
+  if (rc || !grid) return rc;
   const int sp = sched_pref(b_layout);
 #ifdef CSMOE_STAMPS
   struct StampDump {
@@ -398,32 +276,27 @@ static int rowspace_launch(const void* A, int64_t lda, const void* const* b_ptrs
       if (FILE* f = fopen(path, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
       (void)hipFree(buf);
     }
-  } stamp_dump{nullptr, grid, st};
+  } stamp_dump{nullptr, (int64_t)grid, st};
   if (getenv("CSMOE_STAMP_FILE")) {
     (void)hipMalloc(&stamp_dump.buf, (size_t)grid * 64);
     (void)hipMemsetAsync(stamp_dump.buf, 0, (size_t)grid * 64, st);
     (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_stamp_buf), &stamp_dump.buf, sizeof(void*), 0, hipMemcpyHostToDevice, st);
   }
 #endif
-#define LAUNCH_SCHED(S)                                                                                              \
-  do {                                                                                                                \
-    if (b_layout == CSMOE_B_NK) {                                                                                     \
-      if ((rc = set_lds2<gg8_kernel<KC, KC, 0, S>>())) return rc;                                                       \
-      hipLaunchKernelGGL((gg8_kernel<KC, KC, 0, S>), dim3((unsigned)grid), dim3(512), LDS2_BYTES, st, p);             \
-    } else {                                                                                                          \
-      if ((rc = set_lds2<gg8_kernel<KC, KM, 0, S>>())) return rc;                                                       \
-      hipLaunchKernelGGL((gg8_kernel<KC, KM, 0, S>), dim3((unsigned)grid), dim3(512), LDS2_BYTES, st, p);             \
-    }                                                                                                                 \
+#define LAUNCH(...)                                                                                   \
+  do {                                                                                                \
+    if ((rc = set_dyn_lds<gg8_kernel<__VA_ARGS__>, LDS2_BYTES>())) return rc;                         \
+    hipLaunchKernelGGL((gg8_kernel<__VA_ARGS__>), dim3(grid), dim3(512), LDS2_BYTES, st, p);          \
   } while (0)
+  const bool nk_w = b_layout == CSMOE_B_NK;
   if (epilogue == CSMOE_EPI_ACCUM) {      // each layout with its default schedule (sched_pref without CSMOE_GEMM_SCHED)
-    if (b_layout == CSMOE_B_NK) {
-      if ((rc = set_lds2<gg8_kernel<KC, KC, 0, BAL, true>>())) return rc;
-      hipLaunchKernelGGL((gg8_kernel<KC, KC, 0, BAL, true>), dim3((unsigned)grid), dim3(512), LDS2_BYTES, st, p);
-    } else {
-      if ((rc = set_lds2<gg8_kernel<KC, KM, 0, WIDE, true>>())) return rc;
-      hipLaunchKernelGGL((gg8_kernel<KC, KM, 0, WIDE, true>), dim3((unsigned)grid), dim3(512), LDS2_BYTES, st, p);
-    }
-  } else if (sp == BAL) LAUNCH_SCHED(BAL); else LAUNCH_SCHED(WIDE);
+    if (nk_w) LAUNCH(KC, KC, BAL, true); else LAUNCH(KC, KM, WIDE, true);
+  } else if (sp == BAL) {
+    if (nk_w) LAUNCH(KC, KC, BAL); else LAUNCH(KC, KM, BAL);
+  } else {
+    if (nk_w) LAUNCH(KC, KC, WIDE); else LAUNCH(KC, KM, WIDE);
+  }
+#undef LAUNCH
   CSMOE_CHECK_LAUNCH("grouped_gemm(bf16 v2)");
   return CSMOE_OK;
 }

@@ -60,18 +60,10 @@ __global__ void __launch_bounds__(512, 2) gg8c_kernel(CvtArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 2, wn = wave & 3;
 
-  int e, row0, rows, tc0, mt;
   const int nct = (p.NC + BNc - 1) / BNc;
-  {
-    const int total = grouped_total_tiles(p.offsets, p.E, p.single_M, BMc, nct, lane, p.row_part);
-    if ((int)blockIdx.x >= total) return;
-    const int v = xcd_remap(blockIdx.x, total);
-    TilePos tp;
-    if (!grouped_find_tile(p.offsets, p.E, p.single_M, BMc, nct, v, lane, tp, p.row_part)) return;
-    e = tp.e; mt = tp.mt;
-    row0 = tp.o0 + tp.mt * BMc; rows = min(BMc, tp.o1 - row0);
-    tc0 = tp.nt * BNc;
-  }
+  FIND_TILE_OR_RETURN(tp, p.offsets, p.E, p.single_M, BMc, nct, 0, p.row_part);
+  // TILE_VARS_8W plus the row tile's number, in this order (with mt made uniform after the others hipcc allocates other registers)
+  int e = tp.e, mt = tp.mt, row0 = tp.o0 + tp.mt * BMc, rows = min(BMc, tp.o1 - row0), tc0 = tp.nt * BNc;
   e = __builtin_amdgcn_readfirstlane(e);
   mt = __builtin_amdgcn_readfirstlane(mt);
   row0 = __builtin_amdgcn_readfirstlane(row0);
@@ -110,37 +102,15 @@ __global__ void __launch_bounds__(512, 2) gg8c_kernel(CvtArgs p) {
     }
   }
 
-  const int g = lane >> 4, i16 = lane & 15;
-  const int kc_lane = i16 * 128 + ((g ^ (i16 >> 1)) << 4);
-  const int q = i16 >> 2, pp = i16 & 3;
-  const int fk = q | ((g & 1) << 2);
-  const int r_blk0 = wm * 4, c_blk0 = wn * 2;
-  int km_c[2];
-#pragma unroll
-  for (int b = 0; b < 2; ++b) km_c[b] = (8 * g + q) * 256 + (((c_blk0 + b) ^ fk) << 5) + pp * 8;
+  FRAG_LANE_8W(wm, wn);
+  FRAG_KM_BLOCKS(km_c, 2, c_blk0);
 
-  f32x4 acc[4][8];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  ZERO_ACC(acc, 4, 8);
 
   const int nk = (red_len + BKc - 1) / BKc;
 
-#define SLOT(kind, tile) (smem + ((((tile) & 1) * 4 + (kind)) * TILE_B))
 #define ISSUE_RL(tile) dma_tile<KC, 2>(rs_r, SLOT(0, tile), vb_rl, ax_r, (tile) * BKc, red_len, ldr_b, wave)
 #define ISSUE_RH(tile) dma_tile<KC, 2>(rs_r, SLOT(3, tile), vb_rh, ax_r, (tile) * BKc, red_len, ldr_b, wave)
-#define PHASE_SYNC_IN()                                \
-  __builtin_amdgcn_sched_barrier(0);                   \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-  __builtin_amdgcn_s_barrier();                        \
-  __builtin_amdgcn_sched_barrier(0);                   \
-  __builtin_amdgcn_s_setprio(1)
-#define PHASE_SYNC_OUT()                               \
-  __builtin_amdgcn_s_setprio(0);                       \
-  __builtin_amdgcn_sched_barrier(0);                   \
-  __builtin_amdgcn_s_barrier();                        \
-  __builtin_amdgcn_sched_barrier(0)
   // the four fp32 quads of one image of K-tile `tile` (rows past Kd fall off the descriptor: zeros)
 #define LOAD_IMG(im, tile)                                                                           \
   do {                                                                                               \
@@ -223,17 +193,12 @@ int gg8c_rowspace(const void* A, int64_t lda, const void* const* b_ptrs, int64_t
   p.R = A; p.ld_r = lda; p.b_ptrs = b_ptrs; p.single_B = single_B; p.ld_c = ldb; p.copy_ptrs = copy_ptrs; p.single_copy = single_copy;
   p.bias_ptrs = bias_ptrs; p.single_bias = single_bias; p.offsets = offsets; p.E = E; p.single_M = M;
   p.NC = N; p.Kd = Kd; p.C = C; p.C2 = C2; p.aux = aux; p.ldc = ldc; p.epilogue = epilogue; p.act = act;
-  const int nct = (N + BNc - 1) / BNc;
-  const int64_t grid = row_part == 1 ? (int64_t)nct * E : (int64_t)nct * ((M + BMc - 1) / BMc + E);
-  if (grid <= 0) return CSMOE_OK;
-  if (grid > 0x7fffffff) { csmoe_set_error("grouped_gemm_f32w: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
-  static bool done = false;
-  if (!done) {
-    hipError_t er = hipFuncSetAttribute((const void*)gg8c_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDSc_BYTES);
-    if (er != hipSuccess) { csmoe_set_error("hipFuncSetAttribute: %s", hipGetErrorString(er)); return CSMOE_ERR_LAUNCH; }
-    done = true;
-  }
-  hipLaunchKernelGGL(gg8c_kernel, dim3((unsigned)grid), dim3(512), LDSc_BYTES, st, p);
+  const int64_t tiles = row_part == 1 ? (int64_t)((N + BNc - 1) / BNc) * E : rowspace_tiles(M, E, N, BMc, BNc);
+  unsigned grid;
+  int rc = grid_1d("grouped_gemm_f32w", tiles, &grid);
+  if (rc || !grid) return rc;
+  if ((rc = set_dyn_lds<gg8c_kernel, LDSc_BYTES>())) return rc;
+  hipLaunchKernelGGL(gg8c_kernel, dim3(grid), dim3(512), LDSc_BYTES, st, p);
   CSMOE_CHECK_LAUNCH("grouped_gemm_f32w");
   return CSMOE_OK;
 }

@@ -146,31 +146,11 @@ __global__ void __launch_bounds__(512, 2) gg8w_kernel(FastArgs p) {
   const unsigned ldr_b = (unsigned)p.ld_r * 2u, ldc_b = (unsigned)p.ld_c * 2u;
   const int dummy_ax[2] = {0, 0};
 
-  // slot(kind, parity) = (parity * 4 + kind) * 16 KiB with kind RL=0, CL=1, CH=2, RH=3
-#define SLOT(kind, tile) (smem + ((((tile) & 1) * 4 + (kind)) * TILE_B))
+  // SLOT, WAIT_DMA, PHASE_SYNC_IN / _OUT, EPI_SYNC: gemm_tiles.h
 #define ISSUE_RL(D, T, tile) dma_tile<KM, 2>(D.rs_r, SLOT(0, tile), D.vb_rl, dummy_ax, (tile) * BK2, T.red_len, ldr_b, wave)
 #define ISSUE_CL(D, T, tile) dma_tile<KM, 2>(D.rs_c, SLOT(1, tile), D.vb_cl, dummy_ax, (tile) * BK2, T.red_len, ldc_b, wave)
 #define ISSUE_CH(D, T, tile) dma_tile<KM, 2>(D.rs_c, SLOT(2, tile), D.vb_ch, dummy_ax, (tile) * BK2, T.red_len, ldc_b, wave)
 #define ISSUE_RH(D, T, tile) dma_tile<KM, 2>(D.rs_r, SLOT(3, tile), D.vb_rh, dummy_ax, (tile) * BK2, T.red_len, ldr_b, wave)
-#define WAIT_DMA(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-  // barrier A closes a phase's read/issue section (reads retired, counted DMA wait taken), barrier B its MFMA section
-#define PHASE_SYNC_IN()                                \
-  __builtin_amdgcn_sched_barrier(0);                   \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-  __builtin_amdgcn_s_barrier();                        \
-  __builtin_amdgcn_sched_barrier(0);                   \
-  __builtin_amdgcn_s_setprio(1)
-  // epilogue barrier: LDS traffic only.  __syncthreads() would add s_waitcnt vmcnt(0) = wait for the next tile's prefetch and
-  // for this tile's global stores at every pass.
-#define EPI_SYNC()                                     \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-  __builtin_amdgcn_s_barrier();                        \
-  asm volatile("" ::: "memory")
-#define PHASE_SYNC_OUT()                               \
-  __builtin_amdgcn_s_setprio(0);                       \
-  __builtin_amdgcn_sched_barrier(0);                   \
-  __builtin_amdgcn_s_barrier();                        \
-  __builtin_amdgcn_sched_barrier(0)
 
   // ---------------- first tile: descriptors + K-tile 0 ----------------
   TileW cur;
@@ -202,21 +182,11 @@ __global__ void __launch_bounds__(512, 2) gg8w_kernel(FastArgs p) {
     const int wm = wave >> 2, wn = wave & 3;       // row half, column quarter
 
     // ---------------- LDS read addressing ----------------
-    const int g = lane >> 4, i16 = lane & 15;
-    const int q = i16 >> 2, pp = i16 & 3;
-    const int fk = q | ((g & 1) << 2);
-    const int r_blk0 = wm * 4, c_blk0 = wn * 2;    // this wave's 16-wide blocks inside the R / C images
-    int km_r[4], km_c[2];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) km_r[b] = (8 * g + q) * 256 + (((r_blk0 + b) ^ fk) << 5) + pp * 8;
-#pragma unroll
-    for (int b = 0; b < 2; ++b) km_c[b] = (8 * g + q) * 256 + (((c_blk0 + b) ^ fk) << 5) + pp * 8;
+    FRAG_LANE_8W(wm, wn);
+    FRAG_KM_BLOCKS(km_r, 4, r_blk0);
+    FRAG_KM_BLOCKS(km_c, 2, c_blk0);
 
-    f32x4 acc[4][8];   // [column block][row block]
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    ZERO_ACC(acc, 4, 8);           // [column block][row block]
 
     const int nk = (cur.red_len + BK2 - 1) / BK2;
     // ragged tiles: a wave whose strips lie outside the tile skips those reads and MFMAs (it still issues its DMA share)
@@ -427,16 +397,6 @@ int persistent_grid(int64_t tiles_upper) {
   return (int)std::min<int64_t>(tiles_upper, ncu);
 }
 
-int set_lds2() {
-  static bool done = false;
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute((const void*)gg8w_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2_BYTES);
-    if (e != hipSuccess) { csmoe_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return CSMOE_ERR_LAUNCH; }
-    done = true;
-  }
-  return CSMOE_OK;
-}
-
 }  // namespace
 
 int gg8_wgrad(const void* A, int64_t lda, const void* B, int64_t ldb, const int32_t* offsets, int E, int Na, int Nb,
@@ -458,10 +418,10 @@ int gg8_wgrad(const void* A, int64_t lda, const void* B, int64_t ldb, const int3
   // per launch -- and 12 would give four XCDs twice the others' work.  Otherwise: one contiguous chunk of the tile order per XCD.
   const bool deal = offsets && xcd_order && (E % 8 == 0 || E >= 64);
   p.xcd_order = (deal && persistent_grid(grid) % 8 == 0 && persistent_grid(grid) < grid) ? xcd_order : nullptr;
-  if (grid <= 0) return CSMOE_OK;
-  if (grid > 0x7fffffff) { csmoe_set_error("grouped_wgrad: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
-  int rc;
-  if ((rc = set_lds2())) return rc;
+  unsigned n_tiles;
+  int rc = grid_1d("grouped_wgrad", grid, &n_tiles);
+  if (rc || !n_tiles) return rc;
+  if ((rc = set_dyn_lds<gg8w_kernel, LDS2_BYTES>())) return rc;
 #ifdef CSMOE_STAMPS
   static unsigned long long* dbg = nullptr;
   if (!dbg) (void)hipMalloc(&dbg, 24 * 16 * 8);

@@ -63,7 +63,7 @@ struct LoopState {
   char* smem;
   int wave4k;                               // wave * 4 KiB: the wave-uniform part of a piece's LDS destination
   int kc_lane, r_off, c_off;
-  int km_c[8];
+  int km_c[8];                              // K-major column addressing: read by nothing since the K-major form went (see read_c)
 };
 
 // acc += a x b in place (see the header, item 2)
@@ -82,20 +82,13 @@ template <int SL, int KS, int B>
 __device__ __forceinline__ bf16x8 read_r(const LoopState& st) {
   return frag_kc(st.smem + SL * (4 * TILE_B) + st.r_off, st.kc_lane, B, KS);
 }
-// Column fragment B of K-step KS from slot SL: one ds_read_b128 (K-contiguous image) or two transposed 64-bit reads (K-major image).
-// THE K-MAJOR FORM IS CORRECT BUT NOT LAUNCHED (gg4_rowspace_ok takes K-contiguous weights only): beside an LDS-DMA in flight hipcc
-// puts vmcnt(0) in front of every ds_read_b64_tr_b16 BUILTIN (14 ms instead of 4.5 per launch), and both ways around it failed here:
-//   * the transposed reads as inline asm (as the 8-wave kernels have them) are invisible to the waitcnt pass, and in this kernel the
-//     allocator moved their results with v_mov copies placed straight behind the asm, before the data had landed, whenever it had
-//     not given the two halves adjacent registers (full-epilogue build: every tile row of waves 2 and 3 wrong; plain-epilogue
-//     tuning builds: none) -- 4.54 ms against 5.08 for the 8-wave kernel while it happened to work;
-//   * the LDS-DMA as inline asm instead (so that the builtin reads stay tracked) gave wrong 16x16 blocks here and there in BOTH
-//     layouts (hazards between SALU / VALU results and an asm VMEM the recogniser cannot see).
-// The K-major row-space launches (dH, dXs) stay on the 8-wave kernel.
-template <int COLK, int SL, int KS, int B>
+// K-contiguous weights only (gg4_rowspace_ok): the K-major row-space launches (dH, dXs) stay on the 8-wave kernel.  What a K-major
+// column image cost here and the two workarounds that failed are in DESIGN.md section 3 (`gg4_kernel`).  LoopState::km_c and its
+// setup are what is left of that form: dead code, but without it hipcc allocates the registers of BOTH kernels differently
+// (tools/kernel_isa_diff.py), so it goes only with a change that measures the kernel again.
+template <int SL, int KS, int B>
 __device__ __forceinline__ bf16x8 read_c(const LoopState& st) {
-  if constexpr (COLK == KC) return frag_kc(st.smem + SL * (4 * TILE_B) + st.c_off, st.kc_lane, B, KS);
-  else return frag_km(st.smem + SL * (4 * TILE_B) + st.c_off, st.km_c[B], KS);
+  return frag_kc(st.smem + SL * (4 * TILE_B) + st.c_off, st.kc_lane, B, KS);
 }
 
 #ifndef CSMOE_V4_ABL
@@ -124,7 +117,7 @@ __device__ __forceinline__ void dma_piece4(LoopState& st, int tile) {
 #define CSMOE_V4_R0STEP 4
 #endif
 
-template <int COLK, int RBN, int CUR, int W, int I>
+template <int RBN, int CUR, int W, int I>
 __device__ __forceinline__ void slot(f32x4 (&acc)[8][8], LoopState& st, int t2) {
   constexpr int NXT = CUR ^ 1;
   constexpr int gi = I >> 3, ks = gi >> 3, cb = gi & 7, rb = I & 7;
@@ -141,7 +134,7 @@ __device__ __forceinline__ void slot(f32x4 (&acc)[8][8], LoopState& st, int t2) 
   if constexpr (RD && I < 16 * RS && (I % RS) == P) {          // K-step 1's 16 fragments, early: slot CUR is free after them
     constexpr int k = I / RS;
     if constexpr (k < 8) { if constexpr (k < RBN) st.fr1[k] = read_r<CUR, 1, k>(st); }
-    else st.fc1[k - 8] = read_c<COLK, CUR, 1, (k - 8)>(st);
+    else st.fc1[k - 8] = read_c<CUR, 1, (k - 8)>(st);
   }
   if constexpr (I == BAR) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -156,33 +149,33 @@ __device__ __forceinline__ void slot(f32x4 (&acc)[8][8], LoopState& st, int t2) 
   if constexpr (RD && I >= R0 && I < R0 + 16 * R0S && ((I - R0) % R0S) == P0) {
     constexpr int k = (I - R0) / R0S;
     if constexpr (k < 8) { if constexpr (k < RBN) st.fr0[k] = read_r<NXT, 0, k>(st); }
-    else st.fc0[k - 8] = read_c<COLK, NXT, 0, (k - 8)>(st);
+    else st.fc0[k - 8] = read_c<NXT, 0, (k - 8)>(st);
   }
 }
-template <int COLK, int RBN, int CUR, int W, int... Is>
+template <int RBN, int CUR, int W, int... Is>
 __device__ __forceinline__ void k_tile(f32x4 (&acc)[8][8], LoopState& st, int t2, std::integer_sequence<int, Is...>) {
-  (slot<COLK, RBN, CUR, W, Is>(acc, st, t2), ...);
+  (slot<RBN, CUR, W, Is>(acc, st, t2), ...);
 }
 template <int SL, int... Is>
 __device__ __forceinline__ void dma_all(LoopState& st, int tile, std::integer_sequence<int, Is...>) { (dma_piece4<Is, SL>(st, tile), ...); }
-template <int COLK, int RBN, int... Is>
+template <int RBN, int... Is>
 __device__ __forceinline__ void read_first(LoopState& st, std::integer_sequence<int, Is...>) {
   ((Is < RBN ? (void)(st.fr0[Is] = read_r<0, 0, Is>(st)) : (void)0), ...);
-  ((st.fc0[Is] = read_c<COLK, 0, 0, Is>(st)), ...);
+  ((st.fc0[Is] = read_c<0, 0, Is>(st)), ...);
 }
 
-template <int COLK, int RBN, int W>
+template <int RBN, int W>
 __device__ __forceinline__ void k_loop_w(f32x4 (&acc)[8][8], LoopState& st, int nk) {
   using S128 = std::make_integer_sequence<int, 128>;
   for (int s = 0; s < nk; s += 2) {                        // nk is even (gg4_rowspace_ok): the body is two K-tiles, one per slot parity;
-    k_tile<COLK, RBN, 0, W>(acc, st, min(s + 2, nk - 1), S128{});   // K-tiles past the end re-load the last one into a slot nobody reads
-    k_tile<COLK, RBN, 1, W>(acc, st, min(s + 3, nk - 1), S128{});
+    k_tile<RBN, 0, W>(acc, st, min(s + 2, nk - 1), S128{});   // K-tiles past the end re-load the last one into a slot nobody reads
+    k_tile<RBN, 1, W>(acc, st, min(s + 3, nk - 1), S128{});
   }
   settle_last_group(acc);      // in every copy of the loop: the moves that reconcile the copies' register assignments come behind it
 }
 
 // RBN = live 16-row blocks of the wave's quadrant (8, 4 or 0: MFMAs and row-fragment reads of the others are not emitted)
-template <int COLK, int RBN>
+template <int RBN>
 __device__ __forceinline__ void k_loop(f32x4 (&acc)[8][8], LoopState& st, int nk, int wave) {
   using S16 = std::make_integer_sequence<int, 16>;
   dma_all<0>(st, 0, S16{});
@@ -190,16 +183,18 @@ __device__ __forceinline__ void k_loop(f32x4 (&acc)[8][8], LoopState& st, int nk
   asm volatile("s_waitcnt vmcnt(16)" ::: "memory");       // K-tile 0 landed
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
-  read_first<COLK, RBN>(st, std::make_integer_sequence<int, 8>{});
+  read_first<RBN>(st, std::make_integer_sequence<int, 8>{});
   switch (wave) {                                          // wave-uniform: four copies of the loop, one slot shift each
-    case 0: k_loop_w<COLK, RBN, 0>(acc, st, nk); break;
-    case 1: k_loop_w<COLK, RBN, 1>(acc, st, nk); break;
-    case 2: k_loop_w<COLK, RBN, 2>(acc, st, nk); break;
-    default: k_loop_w<COLK, RBN, 3>(acc, st, nk); break;
+    case 0: k_loop_w<RBN, 0>(acc, st, nk); break;
+    case 1: k_loop_w<RBN, 1>(acc, st, nk); break;
+    case 2: k_loop_w<RBN, 2>(acc, st, nk); break;
+    default: k_loop_w<RBN, 3>(acc, st, nk); break;
   }
 }
 
-template <int COLK, bool ACC = false>      // ACC: the CSMOE_EPI_ACCUM epilogue only (gemm_epilogue.h, rowspace_epilogue)
+// COLK is KC always (read_c above); the parameter stays because profiles and tools key on the kernel's name.
+// ACC: the CSMOE_EPI_ACCUM epilogue only (gemm_epilogue.h, rowspace_epilogue)
+template <int COLK, bool ACC = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) gg4_kernel(FastArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
@@ -208,13 +203,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 
   // ---------------- tile lookup: (expert, column tile, row tile) order, one contiguous chunk of it per XCD ----------------
   const int nct = (p.NC + BN4 - 1) / BN4;
-  TilePos tp;
-  {
-    const int total = grouped_total_tiles(p.offsets, p.E, p.single_M, BM4, nct, lane);
-    if ((int)blockIdx.x >= total) return;
-    const int v = xcd_remap(blockIdx.x, total);
-    if (!grouped_find_tile<CSMOE_V4_WHOLE>(p.offsets, p.E, p.single_M, BM4, nct, v, lane, tp)) return;
-  }
+  FIND_TILE_OR_RETURN(tp, p.offsets, p.E, p.single_M, BM4, nct, CSMOE_V4_WHOLE, 0);
   const int e = __builtin_amdgcn_readfirstlane(tp.e);
   const int row0 = __builtin_amdgcn_readfirstlane(tp.o0 + tp.mt * BM4);
   const int rows = __builtin_amdgcn_readfirstlane(min(BM4, tp.o1 - row0));
@@ -234,27 +223,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     dma_setup<KC, 4>(t, ax, ldr_b, 0, 0, 7, 0, 128, wave, lane);
 #pragma unroll
     for (int j = 0; j < 4; ++j) st.vb[4 + j] = t[j];
-    if (COLK == KC) {
-      const int nrows = min(BN4, p.NC - tc0);
-      st.rs_c = make_rsrc(wb + (int64_t)tc0 * ldc_b, (unsigned)nrows * ldc_b);
-      dma_setup<KC, 4>(t, ax, ldc_b, 0, 0, 7, 0, 0, wave, lane);
+    const int nrows = min(BN4, p.NC - tc0);
+    st.rs_c = make_rsrc(wb + (int64_t)tc0 * ldc_b, (unsigned)nrows * ldc_b);
+    dma_setup<KC, 4>(t, ax, ldc_b, 0, 0, 7, 0, 0, wave, lane);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) st.vb[8 + j] = t[j];
-      dma_setup<KC, 4>(t, ax, ldc_b, 0, 0, 7, 0, 128, wave, lane);
+    for (int j = 0; j < 4; ++j) st.vb[8 + j] = t[j];
+    dma_setup<KC, 4>(t, ax, ldc_b, 0, 0, 7, 0, 128, wave, lane);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) st.vb[12 + j] = t[j];
-    } else {
-      st.rs_c = make_rsrc(wb, (unsigned)p.Kd * ldc_b);
-      dma_setup<KM, 4>(t, ax, ldc_b, tc0, p.NC, 7, 0, 0, wave, lane);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) st.vb[8 + j] = t[j];
-      dma_setup<KM, 4>(t, ax, ldc_b, tc0, p.NC, 7, 0, 128, wave, lane);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) st.vb[12 + j] = t[j];
-    }
+    for (int j = 0; j < 4; ++j) st.vb[12 + j] = t[j];
   }
-  st.kstep_r = BK4 * 2u;                                  // bytes one K-tile advances a K-contiguous row (the SGPR offset of the DMA:
-  st.kstep_c = COLK == KC ? BK4 * 2u : BK4 * ldc_b;       // no per-lane K bound is needed, K is a whole number of K-tiles)
+  st.kstep_r = st.kstep_c = BK4 * 2u;                     // bytes one K-tile advances a K-contiguous row (the SGPR offset of the DMA:
+                                                          // no per-lane K bound is needed, K is a whole number of K-tiles)
   {
     const int g = lane >> 4, i16 = lane & 15;
     st.kc_lane = i16 * 128 + ((g ^ (i16 >> 1)) << 4);
@@ -268,19 +247,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     st.wave4k = wave * 4096;
   }
 
-  f32x4 acc[8][8];     // [column block][row block]: rows wm*128 + rb*16 + lane%16, columns wn*128 + cb*16 + 4*(lane/16) + 0..3 (Lay4)
-#pragma unroll
-  for (int a = 0; a < 8; ++a)
-#pragma unroll
-    for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  ZERO_ACC(acc, 8, 8);     // [column block][row block]: rows wm*128 + rb*16 + lane%16, columns wn*128 + cb*16 + 4*(lane/16) + 0..3 (Lay4)
 
   const int nk = p.Kd / BK4;
   // a wave whose rows lie past the expert's range issues its DMA pieces and takes every barrier but no MFMA; the remainder tile of an
   // expert (1..64 rows) keeps half of wave-row 0's
   const int rows_here = rows - wm * 128;
-  if (rows_here > 64) k_loop<COLK, 8>(acc, st, nk, wave);
-  else if (rows_here > 0) k_loop<COLK, 4>(acc, st, nk, wave);
-  else k_loop<COLK, 0>(acc, st, nk, wave);
+  if (rows_here > 64) k_loop<8>(acc, st, nk, wave);
+  else if (rows_here > 0) k_loop<4>(acc, st, nk, wave);
+  else k_loop<0>(acc, st, nk, wave);
 
   // the DMA pieces of the K-tiles past the end have landed and every wave's last fragment reads are done before the staging tile
   // overlays the images
@@ -297,18 +272,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 #endif
 }
 
-// one flag per kernel instantiation (keyed on the kernel, not on the function-pointer type all instantiations share)
-template <auto Kern>
-int set_lds4() {
-  static bool done = false;
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4_BYTES);
-    if (e != hipSuccess) { csmoe_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return CSMOE_ERR_LAUNCH; }
-    done = true;
-  }
-  return CSMOE_OK;
-}
-
 }  // namespace
 
 // shapes the one-wave-per-SIMD kernel takes beyond gg_fast_rowspace_ok: whole PAIRS of K-tiles (the loop body is two K-tiles, one per
@@ -319,24 +282,20 @@ int gg4_rowspace(const void* A, int64_t lda, const void* const* b_ptrs, int b_la
                  const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2,
                  const void* aux, int64_t ldc, int epilogue, int act, const void* single_B, const void* single_bias,
                  hipStream_t st) {
-  FastArgs p{};
-  p.single_M = M; p.single_B = single_B; p.single_bias = single_bias;
-  p.R = A; p.ld_r = lda; p.c_ptrs_in = b_ptrs; p.ld_c = ldb; p.bias_ptrs = bias_ptrs; p.offsets = offsets; p.E = E;
-  p.NC = N; p.Kd = Kd; p.C = C; p.C2 = C2; p.aux = aux; p.ldc = ldc; p.epilogue = epilogue; p.act = act;
-  const int nct = (N + BN4 - 1) / BN4;
-  const int64_t grid = (int64_t)nct * ((M + BM4 - 1) / BM4 + E);
-  if (grid <= 0) return CSMOE_OK;
-  if (grid > 0x7fffffff) { csmoe_set_error("grouped_gemm: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
-  int rc;
-  if (epilogue == CSMOE_EPI_ACCUM) {      // K-contiguous weights only (gg4_rowspace_ok)
-    if ((rc = set_lds4<gg4_kernel<KC, true>>())) return rc;
-    hipLaunchKernelGGL((gg4_kernel<KC, true>), dim3((unsigned)grid), dim3(256), LDS4_BYTES, st, p);
-  } else if (b_layout == CSMOE_B_NK) {
-    if ((rc = set_lds4<gg4_kernel<KC>>())) return rc;
-    hipLaunchKernelGGL((gg4_kernel<KC>), dim3((unsigned)grid), dim3(256), LDS4_BYTES, st, p);
+  const FastArgs p = rowspace_args(A, lda, b_ptrs, ldb, bias_ptrs, offsets, E, M, N, Kd, C, C2, aux, ldc, epilogue, act, single_B, single_bias);
+  unsigned grid;
+  int rc = grid_1d("grouped_gemm", rowspace_tiles(M, E, N, BM4, BN4), &grid);
+  if (rc || !grid) return rc;
+  if (b_layout != CSMOE_B_NK) {           // callers ask gg4_rowspace_ok first
+    csmoe_set_error("grouped_gemm(bf16 v4): K-contiguous weights (CSMOE_B_NK) only");
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  if (epilogue == CSMOE_EPI_ACCUM) {
+    if ((rc = set_dyn_lds<gg4_kernel<KC, true>, LDS4_BYTES>())) return rc;
+    hipLaunchKernelGGL((gg4_kernel<KC, true>), dim3(grid), dim3(256), LDS4_BYTES, st, p);
   } else {
-    if ((rc = set_lds4<gg4_kernel<KM>>())) return rc;
-    hipLaunchKernelGGL((gg4_kernel<KM>), dim3((unsigned)grid), dim3(256), LDS4_BYTES, st, p);
+    if ((rc = set_dyn_lds<gg4_kernel<KC>, LDS4_BYTES>())) return rc;
+    hipLaunchKernelGGL((gg4_kernel<KC>), dim3(grid), dim3(256), LDS4_BYTES, st, p);
   }
   CSMOE_CHECK_LAUNCH("grouped_gemm(bf16 v4)");
   return CSMOE_OK;

@@ -46,22 +46,9 @@ __global__ void __launch_bounds__(512, 2) gg8f_kernel(Fp8Args p) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 2, wn = wave & 3;
 
-  int e, row0, rows, tc0;
   const int nct = (p.NC + BN8 - 1) / BN8;
-  {
-    const int total = grouped_total_tiles(p.offsets, p.E, p.single_M, BM8, nct, lane);
-    if ((int)blockIdx.x >= total) return;
-    const int v = xcd_remap(blockIdx.x, total);
-    TilePos tp;
-    if (!grouped_find_tile(p.offsets, p.E, p.single_M, BM8, nct, v, lane, tp)) return;
-    e = tp.e;
-    row0 = tp.o0 + tp.mt * BM8; rows = min(BM8, tp.o1 - row0);
-    tc0 = tp.nt * BN8;
-  }
-  e = __builtin_amdgcn_readfirstlane(e);
-  row0 = __builtin_amdgcn_readfirstlane(row0);
-  rows = __builtin_amdgcn_readfirstlane(rows);
-  tc0 = __builtin_amdgcn_readfirstlane(tc0);
+  FIND_TILE_OR_RETURN(tp, p.offsets, p.E, p.single_M, BM8, nct, 0, 0);
+  TILE_VARS_8W(tp, BM8, BN8);
   // the DMA helpers count the reduction in 2-byte units (they were written for bf16): 64 units = one 128-byte K-tile
   const int red_len = p.Kd >> 1;
   const int ncols = min(BN8, p.NC - tc0);
@@ -93,15 +80,10 @@ __global__ void __launch_bounds__(512, 2) gg8f_kernel(Fp8Args p) {
   const int f_hi = i16 * 128 + (((g + 4) ^ sw) << 4);          // chunk g + 4
   const int r_blk0 = wm * 4, c_blk0 = wn * 2;
 
-  f32x4 acc[4][8];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  ZERO_ACC(acc, 4, 8);
 
   const int nk = (p.Kd + 127) / 128;
 
-#define SLOT(kind, tile) (smem + ((((tile) & 1) * 4 + (kind)) * TILE_B))
 #define SCSLOT(tile) (smem + SC_OFF + ((tile) & 1) * 2048)
 #define ISSUE_RL(tile) dma_tile<KC, 2>(rs_r, SLOT(0, tile), vb_rl, ax_r, (tile) * 64, red_len, ldr_b, wave)
 #define ISSUE_CL(tile) dma_tile<KC, 2>(rs_c, SLOT(1, tile), vb_cl, ax_c, (tile) * 64, red_len, ldc_b, wave)
@@ -115,18 +97,6 @@ __global__ void __launch_bounds__(512, 2) gg8f_kernel(Fp8Args p) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(sc_rows ? rs_rs : rs_cs, (lds_void*)(SCSLOT(tile) + wave * 256), 4,    \
                                              vo_, 0, 0, 0);                                                         \
   } while (0)
-#define WAIT_DMA(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-#define PHASE_SYNC_IN()                                \
-  __builtin_amdgcn_sched_barrier(0);                   \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-  __builtin_amdgcn_s_barrier();                        \
-  __builtin_amdgcn_sched_barrier(0);                   \
-  __builtin_amdgcn_s_setprio(1)
-#define PHASE_SYNC_OUT()                               \
-  __builtin_amdgcn_s_setprio(0);                       \
-  __builtin_amdgcn_sched_barrier(0);                   \
-  __builtin_amdgcn_s_barrier();                        \
-  __builtin_amdgcn_sched_barrier(0)
 #define FRAG(img, blk) ({                                                              \
     const i32x4 lo_ = *(const i32x4*)((img) + (blk) * 2048 + f_lo);                     \
     const i32x4 hi_ = *(const i32x4*)((img) + (blk) * 2048 + f_hi);                     \
@@ -138,50 +108,7 @@ __global__ void __launch_bounds__(512, 2) gg8f_kernel(Fp8Args p) {
   const int cols_here = ncols - wn * 32;
   const bool rlo = rows_here > 0, rhi = rows_here > 128, clo = cols_here > 0, chi = cols_here > 128;
 
-  if (rows <= 128) {
-    // Thin tile (the remainder tile of an expert: at 128 experts x ~512 rows half of the experts end in one of a few dozen rows):
-    // the one-phase loop of gemm_bf16_v2.hip -- no RH image, one barrier pair and 7 pieces per K-tile, every wave's 4 x 4 blocks
-    // of C_all x R_lo in one MFMA section.
-    ISSUE_CL(0); ISSUE_CH(0); ISSUE_RL(0); ISSUE_SC(0); ISSUE_CL(1); ISSUE_CH(1); ISSUE_RL(1); ISSUE_SC(1);
-    WAIT_DMA(7);                                           // K-tile 0 landed
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-#define THIN_FRAG_DECL const char* sc = SCSLOT(s); i32x8 fc[4], fr[4]; int sc_c[4], sc_r[4];
-#define THIN_READ_CL(cb) fc[cb] = FRAG(i_cl, c_blk0 + cb); sc_c[cb] = *(const uint8_t*)(sc + 1024 + ((c_blk0 + cb) * 16 + i16) * 4 + g);
-#define THIN_READ_CH(cb) fc[2 + cb] = FRAG(i_ch, c_blk0 + cb); sc_c[2 + cb] = *(const uint8_t*)(sc + 1024 + (128 + (c_blk0 + cb) * 16 + i16) * 4 + g);
-#define THIN_READ_RL(rb) fr[rb] = FRAG(i_rl, r_blk0 + rb); sc_r[rb] = *(const uint8_t*)(sc + ((r_blk0 + rb) * 16 + i16) * 4 + g);
-#define THIN_KSTEPS 1
-#define THIN_MFMA(ks, cb, rb) MFMA8(acc[cb][rb], fc[cb], fr[rb], sc_c[cb], sc_r[rb]);
-#define THIN_ISSUE(s) ISSUE_CL(s + 2); ISSUE_CH(s + 2); ISSUE_RL(s + 2); ISSUE_SC(s + 2)
-#define THIN_WAIT(s) WAIT_DMA(7)                           /* K-tile s+1 landed (s+2 stays in flight) */
-#include "gemm_loop_thin.inc"
-  } else {
-  // issue order ... [CL,CH,RL,SC](s+1) | RH(s+1) | [CL,CH,RL,SC](s+2) | RH(s+2) ...: 7 + 2 pieces per K-tile and wave, so the
-  // counted waits of the bf16 loop (8) become 9
-  ISSUE_CL(0); ISSUE_CH(0); ISSUE_RL(0); ISSUE_SC(0); ISSUE_RH(0); ISSUE_CL(1); ISSUE_CH(1); ISSUE_RL(1); ISSUE_SC(1);
-  WAIT_DMA(9);                                           // CL, CH, RL, SC(0) landed
-  __builtin_amdgcn_s_barrier();
-  if (wm == 1) __builtin_amdgcn_s_barrier();             // row half 1 starts half a phase late
-  __builtin_amdgcn_sched_barrier(0);
-  // phase A also reads ALL scales of K-tile s (the RH rows' too); a K = 128 MFMA per (column block, row block) and K-tile
-#define BAL_FRAG_DECL const char* sc = SCSLOT(s); i32x8 fc[4], fr[4]; int sc_c[4], sc_r[8];
-#define BAL_READ_CL(cb) fc[cb] = FRAG(i_cl, c_blk0 + cb); sc_c[cb] = *(const uint8_t*)(sc + 1024 + ((c_blk0 + cb) * 16 + i16) * 4 + g);
-#define BAL_READ_CH(cb) fc[2 + cb] = FRAG(i_ch, c_blk0 + cb); sc_c[2 + cb] = *(const uint8_t*)(sc + 1024 + (128 + (c_blk0 + cb) * 16 + i16) * 4 + g);
-#define BAL_READ_RL(rb) fr[rb] = FRAG(i_rl, r_blk0 + rb); sc_r[rb] = *(const uint8_t*)(sc + ((r_blk0 + rb) * 16 + i16) * 4 + g);
-#define BAL_READ_RH(rb) fr[rb] = FRAG(i_rh, r_blk0 + rb);
-#define BAL_PHASE_A_EXTRA                                                                                                      \
-  if (rhi && clo) {                                                                                                            \
-    _Pragma("unroll") for (int rb = 0; rb < 4; ++rb) sc_r[4 + rb] = *(const uint8_t*)(sc + (128 + (r_blk0 + rb) * 16 + i16) * 4 + g); \
-  }
-#define BAL_KSTEPS 1
-#define BAL_MFMA(ks, cb, rb, arb) MFMA8(acc[cb][arb], fc[cb], fr[rb], sc_c[cb], sc_r[arb]);
-#define BAL_ISSUE_A(s) ISSUE_RH(s + 1)
-#define BAL_ISSUE_B(s) ISSUE_CL(s + 2); ISSUE_CH(s + 2); ISSUE_RL(s + 2); ISSUE_SC(s + 2)
-#define BAL_WAIT_A(s) WAIT_DMA(9)                          /* RH(s) landed */
-#define BAL_WAIT_B(s) WAIT_DMA(9)                          /* CL, CH, RL, SC(s+1) landed */
-#include "gemm_loop_bal.inc"
-  if (wm == 0) __builtin_amdgcn_s_barrier();
-  }
+#include "gemm_loop_fp8.inc"
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -203,17 +130,11 @@ int gg8f_rowspace(const void* Aq, int64_t lda, const void* As, int64_t ldas, con
   p.c_ptrs = bq_ptrs; p.cs_ptrs = bs_ptrs; p.ld_c = ldb; p.ld_cs = ldbs; p.single_B = single_B; p.single_BS = single_BS;
   p.bias_ptrs = bias_ptrs; p.single_bias = single_bias; p.offsets = offsets; p.E = E; p.single_M = M;
   p.NC = N; p.Kd = Kd; p.C = C; p.C2 = C2; p.aux = aux; p.ldc = ldc; p.epilogue = epilogue; p.act = act;
-  const int nct = (N + BN8 - 1) / BN8;
-  const int64_t grid = (int64_t)nct * ((M + BM8 - 1) / BM8 + E);
-  if (grid <= 0) return CSMOE_OK;
-  if (grid > 0x7fffffff) { csmoe_set_error("grouped_gemm_mxfp8: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
-  static bool done = false;
-  if (!done) {
-    hipError_t er = hipFuncSetAttribute((const void*)gg8f_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
-    if (er != hipSuccess) { csmoe_set_error("hipFuncSetAttribute: %s", hipGetErrorString(er)); return CSMOE_ERR_LAUNCH; }
-    done = true;
-  }
-  hipLaunchKernelGGL(gg8f_kernel, dim3((unsigned)grid), dim3(512), LDS8_BYTES, st, p);
+  unsigned grid;
+  int rc = grid_1d("grouped_gemm_mxfp8", rowspace_tiles(M, E, N, BM8, BN8), &grid);
+  if (rc || !grid) return rc;
+  if ((rc = set_dyn_lds<gg8f_kernel, LDS8_BYTES>())) return rc;
+  hipLaunchKernelGGL(gg8f_kernel, dim3(grid), dim3(512), LDS8_BYTES, st, p);
   CSMOE_CHECK_LAUNCH("grouped_gemm_mxfp8");
   return CSMOE_OK;
 }
@@ -223,7 +144,7 @@ int gg8f_rowspace(const void* Aq, int64_t lda, const void* As, int64_t ldas, con
 // csmoe_quantize_mxfp8_tokens: At [Na, n_pad] / Bt [Nb, n_pad] e4m3, contiguous along k, scales [., n_pad/32], every expert's k range
 // a multiple of 128 long and zero-padded, so that a K-tile never mixes two experts and the last one needs no masking.  An NT
 // product with a K range per tile, assembled from two kernels the project already has:
-//   * the K-loop, fragments, scale DMA and MFMA of gg8f_kernel above, unchanged (the A operand takes the place of the token rows,
+//   * the K-loop, fragments, scale DMA and MFMA of gg8f_kernel above, unchanged (one text: gemm_loop_fp8.inc; the A operand takes the place of the token rows,
 //     the B operand that of the weight rows; the operand and scale descriptors start at the expert's first k);
 //   * the persistent tile walk of gg8w_kernel (gemm_bf16_v2p.hip): one workgroup per CU walks its XCD's contiguous chunk of the
 //     expert-major tile order, or the experts dealt to its XCD (`xcd_order`), in bands of row tiles, and its store epilogue
@@ -311,56 +232,15 @@ __global__ void __launch_bounds__(512, 2) gg8wf_kernel(Fp8WArgs p) {
     const int f_hi = i16 * 128 + (((g + 4) ^ sw) << 4);
     const int r_blk0 = wm * 4, c_blk0 = wn * 2;
 
-    f32x4 acc[4][8];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    ZERO_ACC(acc, 4, 8);
 
     const int nk = kd >> 7;
     const int rows_here = rows - wm * 64;
     const int cols_here = ncols - wn * 32;
     const bool rlo = rows_here > 0, rhi = rows_here > 128, clo = cols_here > 0, chi = cols_here > 128;
 
-    // ---------------- K-loop: gg8f_kernel's, hook for hook (SLOT / ISSUE_* / FRAG / MFMA8 as defined there) ----------------
-    if (rows <= 128) {
-      ISSUE_CL(0); ISSUE_CH(0); ISSUE_RL(0); ISSUE_SC(0); ISSUE_CL(1); ISSUE_CH(1); ISSUE_RL(1); ISSUE_SC(1);
-      WAIT_DMA(7);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-#define THIN_FRAG_DECL const char* sc = SCSLOT(s); i32x8 fc[4], fr[4]; int sc_c[4], sc_r[4];
-#define THIN_READ_CL(cb) fc[cb] = FRAG(i_cl, c_blk0 + cb); sc_c[cb] = *(const uint8_t*)(sc + 1024 + ((c_blk0 + cb) * 16 + i16) * 4 + g);
-#define THIN_READ_CH(cb) fc[2 + cb] = FRAG(i_ch, c_blk0 + cb); sc_c[2 + cb] = *(const uint8_t*)(sc + 1024 + (128 + (c_blk0 + cb) * 16 + i16) * 4 + g);
-#define THIN_READ_RL(rb) fr[rb] = FRAG(i_rl, r_blk0 + rb); sc_r[rb] = *(const uint8_t*)(sc + ((r_blk0 + rb) * 16 + i16) * 4 + g);
-#define THIN_KSTEPS 1
-#define THIN_MFMA(ks, cb, rb) MFMA8(acc[cb][rb], fc[cb], fr[rb], sc_c[cb], sc_r[rb]);
-#define THIN_ISSUE(s) ISSUE_CL(s + 2); ISSUE_CH(s + 2); ISSUE_RL(s + 2); ISSUE_SC(s + 2)
-#define THIN_WAIT(s) WAIT_DMA(7)
-#include "gemm_loop_thin.inc"
-    } else {
-      ISSUE_CL(0); ISSUE_CH(0); ISSUE_RL(0); ISSUE_SC(0); ISSUE_RH(0); ISSUE_CL(1); ISSUE_CH(1); ISSUE_RL(1); ISSUE_SC(1);
-      WAIT_DMA(9);
-      __builtin_amdgcn_s_barrier();
-      if (wm == 1) __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-#define BAL_FRAG_DECL const char* sc = SCSLOT(s); i32x8 fc[4], fr[4]; int sc_c[4], sc_r[8];
-#define BAL_READ_CL(cb) fc[cb] = FRAG(i_cl, c_blk0 + cb); sc_c[cb] = *(const uint8_t*)(sc + 1024 + ((c_blk0 + cb) * 16 + i16) * 4 + g);
-#define BAL_READ_CH(cb) fc[2 + cb] = FRAG(i_ch, c_blk0 + cb); sc_c[2 + cb] = *(const uint8_t*)(sc + 1024 + (128 + (c_blk0 + cb) * 16 + i16) * 4 + g);
-#define BAL_READ_RL(rb) fr[rb] = FRAG(i_rl, r_blk0 + rb); sc_r[rb] = *(const uint8_t*)(sc + ((r_blk0 + rb) * 16 + i16) * 4 + g);
-#define BAL_READ_RH(rb) fr[rb] = FRAG(i_rh, r_blk0 + rb);
-#define BAL_PHASE_A_EXTRA                                                                                                      \
-  if (rhi && clo) {                                                                                                            \
-    _Pragma("unroll") for (int rb = 0; rb < 4; ++rb) sc_r[4 + rb] = *(const uint8_t*)(sc + (128 + (r_blk0 + rb) * 16 + i16) * 4 + g); \
-  }
-#define BAL_KSTEPS 1
-#define BAL_MFMA(ks, cb, rb, arb) MFMA8(acc[cb][arb], fc[cb], fr[rb], sc_c[cb], sc_r[arb]);
-#define BAL_ISSUE_A(s) ISSUE_RH(s + 1)
-#define BAL_ISSUE_B(s) ISSUE_CL(s + 2); ISSUE_CH(s + 2); ISSUE_RL(s + 2); ISSUE_SC(s + 2)
-#define BAL_WAIT_A(s) WAIT_DMA(9)
-#define BAL_WAIT_B(s) WAIT_DMA(9)
-#include "gemm_loop_bal.inc"
-      if (wm == 0) __builtin_amdgcn_s_barrier();
-    }
+    // ---------------- K-loop: gg8f_kernel's (SLOT / ISSUE_* / FRAG / MFMA8 as defined there) ----------------
+#include "gemm_loop_fp8.inc"
     // the zero-fill DMAs of the K-tiles past the end may still be writing LDS: drain before the staging tile overlays the slots
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -386,9 +266,7 @@ __global__ void __launch_bounds__(512, 2) gg8wf_kernel(Fp8WArgs p) {
           const int n = (cb >> 1) * 128 + wn * 32 + (cb & 1) * 16 + 4 * g;
           *(f32x4*)(stg + m * CT8_LD + n) = acc[cb][4 * h + 2 * u + i];
         }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      EPI_SYNC();
       if (p.out_f32) {
         // one store instruction = one 1-KiB row segment (64 lanes x 16 B)
         const int ec4 = lane * 4, er8 = wave;
@@ -438,9 +316,7 @@ __global__ void __launch_bounds__(512, 2) gg8wf_kernel(Fp8WArgs p) {
           }
         }
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // every thread's staging reads retired before the next pass / tile
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      EPI_SYNC();                                          // every thread's staging reads retired before the next pass / tile
     }
   }   // persistent tile loop
 }
@@ -468,18 +344,14 @@ int gg8f_wgrad(const void* Aq, int64_t lda, const void* As, int64_t ldas, const 
   p.out_ptrs = c_ptrs; p.ldc = ldc; p.accumulate = accumulate; p.out_f32 = out_dtype == CSMOE_F32;
   p.tile_band = E > 1 ? 5 : 4;                   // gg8_wgrad's band heights
   const int64_t tiles = (int64_t)E * ((Na + BM8 - 1) / BM8) * ((Nb + BN8 - 1) / BN8);
-  if (tiles <= 0) return CSMOE_OK;
-  if (tiles > 0x7fffffff) { csmoe_set_error("grouped_wgrad_mxfp8: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
+  unsigned n_tiles;
+  int rc = grid_1d("grouped_wgrad_mxfp8", tiles, &n_tiles);
+  if (rc || !n_tiles) return rc;
   const int grid = fp8w_grid(tiles);
   // dealing needs whole experts per XCD and a grid that is a multiple of 8 (gg8_wgrad)
   const bool deal = xcd_order && (E % 8 == 0 || E >= 64) && grid % 8 == 0 && grid < tiles;
   p.xcd_order = deal ? xcd_order : nullptr;
-  static bool done = false;
-  if (!done) {
-    hipError_t er = hipFuncSetAttribute((const void*)gg8wf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8_BYTES);
-    if (er != hipSuccess) { csmoe_set_error("hipFuncSetAttribute: %s", hipGetErrorString(er)); return CSMOE_ERR_LAUNCH; }
-    done = true;
-  }
+  if ((rc = set_dyn_lds<gg8wf_kernel, LDS8_BYTES>())) return rc;
   hipLaunchKernelGGL(gg8wf_kernel, dim3((unsigned)grid), dim3(512), LDS8_BYTES, st, p);
   CSMOE_CHECK_LAUNCH("grouped_wgrad_mxfp8");
   return CSMOE_OK;

@@ -86,10 +86,7 @@ __global__ void __launch_bounds__(NW * 64) skinny_kernel(SkinnyArgs p) {
 
   // ---------------- tile lookup (wave-uniform) ----------------
   const int ncs = (p.N + SLAB - 1) / SLAB;
-  const int total = grouped_total_tiles(p.offsets, p.E, p.M, 16, ncs, lane);
-  if ((int)blockIdx.x >= total) return;
-  TilePos tp;
-  if (!grouped_find_tile(p.offsets, p.E, p.M, 16, ncs, xcd_remap(blockIdx.x, total), lane, tp)) return;
+  FIND_TILE_OR_RETURN(tp, p.offsets, p.E, p.M, 16, ncs, 0, 0);
   const int e = __builtin_amdgcn_readfirstlane(tp.e);
   const int row0 = __builtin_amdgcn_readfirstlane(tp.o0 + tp.mt * 16);
   const int rows = __builtin_amdgcn_readfirstlane(min(16, tp.o1 - row0));
@@ -184,30 +181,13 @@ __global__ void __launch_bounds__(NW * 64) skinny_kernel(SkinnyArgs p) {
 
   // ---------------- the 8 partial tiles meet in LDS (overlaying the B_KN images) ----------------
   __syncthreads();
-  {
-    float* red = (float*)smem + wave * (16 * LDW);
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) *(f32x4*)(red + i16 * LDW + nb * 16 + 4 * g) = acc[nb];
-  }
-  __syncthreads();
+  SKINNY_STORE_PARTIAL((float*)smem, acc);
 
   // ---------------- epilogue: thread (r, cg) owns 8 columns of one row ----------------
   const int r = threadIdx.x / CPR, cg = threadIdx.x % CPR;
   const int ncol = n0 + cg * 8;
   if (r >= rows || ncol >= p.N) return;
-  float v[8];
-  {
-    const float* red = (const float*)smem + r * LDW + cg * 8;
-    const f32x4 lo = *(const f32x4*)red, hi = *(const f32x4*)(red + 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[j] = lo[j]; v[4 + j] = hi[j]; }
-#pragma unroll
-    for (int w = 1; w < NW; ++w) {                    // wave order: the one summation order of every run
-      const f32x4 l2 = *(const f32x4*)(red + w * 16 * LDW), h2 = *(const f32x4*)(red + w * 16 * LDW + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { v[j] += l2[j]; v[4 + j] += h2[j]; }
-    }
-  }
+  SKINNY_SUM_PARTIALS(v, (float*)smem, r, cg);
   float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const bool post_bias = p.epilogue == CSMOE_EPI_ROUND_BIAS32_ACT;     // fp32 bias added to the ROUNDED product (cvmm + bias)
   if (p.epilogue != CSMOE_EPI_PLAIN) {
@@ -256,17 +236,16 @@ int gg_skinny_rowspace(const void* A, int64_t lda, const int32_t* src_rows, int 
   p.A = (const bf16*)A; p.lda = lda; p.src_rows = src_rows; p.src_div = src_rows ? src_div : 1;
   p.b_ptrs = b_ptrs; p.ldb = ldb; p.bias_ptrs = bias_ptrs; p.offsets = offsets; p.E = E; p.M = M; p.N = N; p.Kd = Kd;
   p.C = (bf16*)C; p.C2 = (bf16*)C2; p.ldc = ldc; p.epilogue = epilogue; p.act = act;
-  // 16-row blocks: sum_e ceil(count_e / 16) <= min(M, M / 16 + E) whatever the counts are
-  const int64_t nrb = std::min<int64_t>(M, (int64_t)M / 16 + E);
+  const int64_t nrb = skinny_row_blocks(M, E);
   // the wider slab (half the token-row loads per weight byte; 128-byte k-row pieces for B_KN) once it still gives two workgroups
   // per CU; the narrow one below that
   const int big = b_layout == CSMOE_B_NK ? 2 : 4;
   const bool wide = nrb * ((N + 16 * big - 1) / (16 * big)) >= 512;
   const int nb = wide ? big : big / 2;
-  const int64_t grid = nrb * ((N + 16 * nb - 1) / (16 * nb));
-  if (grid <= 0) return CSMOE_OK;
-  if (grid > 0x7fffffff) { csmoe_set_error("grouped_gemm_skinny: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
-  const dim3 gr((unsigned)grid), bl(NW * 64);
+  unsigned grid;
+  const int rc = grid_1d("grouped_gemm_skinny", nrb * ((N + 16 * nb - 1) / (16 * nb)), &grid);
+  if (rc || !grid) return rc;
+  const dim3 gr(grid), bl(NW * 64);
   if (b_layout == CSMOE_B_NK) {
     if (nb == 2) hipLaunchKernelGGL((skinny_kernel<CSMOE_B_NK, 2>), gr, bl, 0, st, p);
     else hipLaunchKernelGGL((skinny_kernel<CSMOE_B_NK, 1>), gr, bl, 0, st, p);

@@ -95,10 +95,7 @@ __global__ void __launch_bounds__(NW * 64, 4) skinny8_kernel(Skinny8Args p) {
 
   // ---------------- tile lookup (wave-uniform) ----------------
   const int ncs = (p.N + SLAB - 1) / SLAB;
-  const int total = grouped_total_tiles(p.offsets, p.E, p.M, 16, ncs, lane);
-  if ((int)blockIdx.x >= total) return;
-  TilePos tp;
-  if (!grouped_find_tile(p.offsets, p.E, p.M, 16, ncs, xcd_remap(blockIdx.x, total), lane, tp)) return;
+  FIND_TILE_OR_RETURN(tp, p.offsets, p.E, p.M, 16, ncs, 0, 0);
   const int e = __builtin_amdgcn_readfirstlane(tp.e);
   const int row0 = __builtin_amdgcn_readfirstlane(tp.o0 + tp.mt * 16);
   const int rows = __builtin_amdgcn_readfirstlane(min(16, tp.o1 - row0));
@@ -178,31 +175,14 @@ __global__ void __launch_bounds__(NW * 64, 4) skinny8_kernel(Skinny8Args p) {
   }
 
   // ---------------- the 8 partial tiles meet in LDS ----------------
-  {
-    float* red = red_s + wave * (16 * LDW);
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) *(f32x4*)(red + i16 * LDW + nb * 16 + 4 * g) = acc[nb];
-  }
-  __syncthreads();
+  SKINNY_STORE_PARTIAL(red_s, acc);
 
   // ---------------- epilogue: thread (r, cg) owns 8 columns of one row; whole waves past the 16 rows leave ----------------
   if (threadIdx.x >= 16 * CPR) return;
   const int r = threadIdx.x / CPR, cg = threadIdx.x % CPR;
   const int ncol = n0 + cg * 8;
   const bool live = r < rows && ncol < p.N;           // the others stay for the shuffles only
-  float v[8];
-  {
-    const float* red = red_s + r * LDW + cg * 8;
-    const f32x4 lo = *(const f32x4*)red, hi = *(const f32x4*)(red + 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[j] = lo[j]; v[4 + j] = hi[j]; }
-#pragma unroll
-    for (int w = 1; w < NW; ++w) {                    // wave order: the one summation order of every run
-      const f32x4 l2 = *(const f32x4*)(red + w * 16 * LDW), h2 = *(const f32x4*)(red + w * 16 * LDW + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { v[j] += l2[j]; v[4 + j] += h2[j]; }
-    }
-  }
+  SKINNY_SUM_PARTIALS(v, red_s, r, cg);
   float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (p.epilogue != CSMOE_EPI_PLAIN && live) {
     const void* bias = p.bias_ptrs ? p.bias_ptrs[e] : nullptr;
@@ -265,15 +245,14 @@ int gg_skinny8_rowspace(const void* Aq, int64_t lda, const void* As, int64_t lda
   p.offsets = offsets; p.E = E; p.M = M; p.N = N; p.Kd = Kd;
   p.C = (bf16*)C; p.C2 = (bf16*)C2; p.ldc = ldc; p.Cq = (uint8_t*)Cq; p.Cs = (uint8_t*)Cs; p.ldcq = ldcq; p.ldcs = ldcs;
   p.epilogue = epilogue; p.act = act;
-  // 16-row blocks: sum_e ceil(count_e / 16) <= min(M, M / 16 + E) whatever the counts are
-  const int64_t nrb = std::min<int64_t>(M, (int64_t)M / 16 + E);
+  const int64_t nrb = skinny_row_blocks(M, E);
   // the 64-column slab (half the token-row loads per weight byte) once it still gives two workgroups per CU; 32 columns below that
   const bool wide = nrb * ((N + 63) / 64) >= 512;
   const int slab = wide ? 64 : 32;
-  const int64_t grid = nrb * ((N + slab - 1) / slab);
-  if (grid <= 0) return CSMOE_OK;
-  if (grid > 0x7fffffff) { csmoe_set_error("grouped_gemm_skinny_mxfp8: grid too large"); return CSMOE_ERR_UNSUPPORTED; }
-  const dim3 gr((unsigned)grid), bl(NW * 64);
+  unsigned grid;
+  const int rc = grid_1d("grouped_gemm_skinny_mxfp8", nrb * ((N + slab - 1) / slab), &grid);
+  if (rc || !grid) return rc;
+  const dim3 gr(grid), bl(NW * 64);
   if (wide) hipLaunchKernelGGL((skinny8_kernel<4>), gr, bl, 0, st, p);
   else hipLaunchKernelGGL((skinny8_kernel<2>), gr, bl, 0, st, p);
   CSMOE_CHECK_LAUNCH("grouped_gemm_skinny_mxfp8");

@@ -33,9 +33,84 @@ struct FastArgs {
   int thin_loop;                              // row-space v2: tiles of <= 128 rows take the one-phase loop
 };
 
+// the fields every row-space launch of FastArgs kernels fills (gg8_rowspace, gg4_rowspace)
+inline FastArgs rowspace_args(const void* A, int64_t lda, const void* const* b_ptrs, int64_t ldb, const void* const* bias_ptrs,
+                              const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2, const void* aux, int64_t ldc,
+                              int epilogue, int act, const void* single_B, const void* single_bias) {
+  FastArgs p{};
+  p.single_M = M; p.single_B = single_B; p.single_bias = single_bias;
+  p.R = A; p.ld_r = lda; p.c_ptrs_in = b_ptrs; p.ld_c = ldb; p.bias_ptrs = bias_ptrs; p.offsets = offsets; p.E = E;
+  p.NC = N; p.Kd = Kd; p.C = C; p.C2 = C2; p.aux = aux; p.ldc = ldc; p.epilogue = epilogue; p.act = act;
+  return p;
+}
+
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
 }
+
+// ---- scaffolding of the 256 x 256 tile kernels, shared as TEXT (macros, like the gemm_loop_*.inc K-loops): these kernels are
+// sensitive to what hipcc hoists and how it allocates registers, and a macro keeps each kernel's code what it was when written in
+// place (tools/kernel_isa_diff.py is the check).  In scope where they are used: smem, lane, and the names they declare.
+// slot(kind, parity) = (parity * 4 + kind) * 16 KiB with kind RL=0, CL=1, CH=2, RH=3
+#define SLOT(kind, tile) (smem + ((((tile) & 1) * 4 + (kind)) * TILE_B))
+#define WAIT_DMA(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
+// barrier A closes a phase's read/issue section (reads retired, counted DMA wait taken), barrier B its MFMA section
+#define PHASE_SYNC_IN()                                \
+  __builtin_amdgcn_sched_barrier(0);                   \
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
+  __builtin_amdgcn_s_barrier();                        \
+  __builtin_amdgcn_sched_barrier(0);                   \
+  __builtin_amdgcn_s_setprio(1)
+#define PHASE_SYNC_OUT()                               \
+  __builtin_amdgcn_s_setprio(0);                       \
+  __builtin_amdgcn_sched_barrier(0);                   \
+  __builtin_amdgcn_s_barrier();                        \
+  __builtin_amdgcn_sched_barrier(0)
+// epilogue barrier: LDS traffic only.  __syncthreads() would add s_waitcnt vmcnt(0) = a wait for the pass's own global stores (and,
+// in the persistent weight gradient, for the next tile's prefetch) at every pass.
+#define EPI_SYNC()                                     \
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
+  __builtin_amdgcn_s_barrier();                        \
+  asm volatile("" ::: "memory")
+
+// Row-space tile lookup: declares TilePos tp, this workgroup's tile; a workgroup past the last tile RETURNS from the kernel.
+// WHOLE / part: grouped_find_tile.
+#define FIND_TILE_OR_RETURN(tp, offsets_, E_, M_, BMt, nct_, WHOLE, part)                                              \
+  TilePos tp;                                                                                                          \
+  {                                                                                                                    \
+    const int total = grouped_total_tiles(offsets_, E_, M_, BMt, nct_, lane, part);                                    \
+    if ((int)blockIdx.x >= total) return;                                                                              \
+    if (!grouped_find_tile<WHOLE>(offsets_, E_, M_, BMt, nct_, xcd_remap(blockIdx.x, total), lane, tp, part)) return;  \
+  }
+// the 8-wave kernels' wave-uniform e (expert), row0 / rows (the tile's rows of the row operand) and tc0 (first output column) of tp.
+// (gg4_kernel and the decode kernels take `rows` from the UNIFORM row0, which compiles to other code: they keep their own lines.)
+#define TILE_VARS_8W(tp, BMt, BNt)                                                                                     \
+  int e = tp.e, row0 = tp.o0 + tp.mt * (BMt), rows = min(BMt, tp.o1 - row0), tc0 = tp.nt * (BNt);                      \
+  e = __builtin_amdgcn_readfirstlane(e);                                                                               \
+  row0 = __builtin_amdgcn_readfirstlane(row0);                                                                         \
+  rows = __builtin_amdgcn_readfirstlane(rows);                                                                         \
+  tc0 = __builtin_amdgcn_readfirstlane(tc0)
+
+// LDS read addressing of the 8-wave kernels' fragments for wave (wm, wn): this lane's offset in a K-contiguous block (kc_lane, for
+// frag_kc) and the wave's first 16-row / 16-column block inside an R / C image (wm*4 + 0..3, wn*2 + 0..1) ...
+#define FRAG_LANE_8W(wm_, wn_)                                                                                         \
+  const int g = lane >> 4, i16 = lane & 15;                                                                            \
+  const int kc_lane = i16 * 128 + ((g ^ (i16 >> 1)) << 4);                                                             \
+  const int q = i16 >> 2, pp = i16 & 3;                                                                                \
+  const int fk = q | ((g & 1) << 2);                                                                                   \
+  const int r_blk0 = (wm_) * 4, c_blk0 = (wn_) * 2;                                                                    \
+  (void)kc_lane; (void)r_blk0
+// ... and, for the kernels with K-major images, its offsets of the N blocks from blk0_ on (km_[], for frag_km_raw).  Declared only
+// where they are read: the unused arrays changed gg8c_kernel's register allocation
+#define FRAG_KM_BLOCKS(km_, N, blk0_)                                                                                  \
+  int km_[N];                                                                                                          \
+  _Pragma("unroll") for (int b = 0; b < N; ++b) km_[b] = (8 * g + q) * 256 + ((((blk0_) + b) ^ fk) << 5) + pp * 8
+
+// f32x4 acc[NA][NB], zeroed
+#define ZERO_ACC(acc_, NA, NB)                                                                                         \
+  f32x4 acc_[NA][NB];                                                                                                  \
+  _Pragma("unroll") for (int a_ = 0; a_ < NA; ++a_)                                                                    \
+    _Pragma("unroll") for (int b_ = 0; b_ < NB; ++b_) acc_[a_][b_] = f32x4{0.f, 0.f, 0.f, 0.f}
 
 
 // Scalar (SMEM) load of 8 bytes from a wave-uniform address (the persistent weight-gradient kernels' table reads).  Written as asm because hipcc turns a plain load of the offsets /
@@ -112,6 +187,27 @@ __device__ __forceinline__ void dma_setup(unsigned (&vbase)[NJ], int (&aux)[NJ],
     }
   }
 }
+
+// ---- the decode kernels (gemm_skinny.hip, gemm_skinny_fp8.hip): the NW waves' partial 16 x SLAB tiles (acc[NB]) meet in LDS at
+// red_ (NW tiles of 16 rows x LDW floats) ...
+#define SKINNY_STORE_PARTIAL(red_, acc_)                                                                               \
+  {                                                                                                                    \
+    float* red = (red_) + wave * (16 * LDW);                                                                           \
+    _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) *(f32x4*)(red + i16 * LDW + nb * 16 + 4 * g) = acc_[nb];         \
+  }                                                                                                                    \
+  __syncthreads()
+// ... and thread (r_, cg_) of the epilogue sums its 8 columns into float v_[8] in wave order 0..7: the one summation order of every run
+#define SKINNY_SUM_PARTIALS(v_, red_, r_, cg_)                                                                         \
+  float v_[8];                                                                                                         \
+  {                                                                                                                    \
+    const float* red = (red_) + (r_) * LDW + (cg_) * 8;                                                                \
+    const f32x4 lo = *(const f32x4*)red, hi = *(const f32x4*)(red + 4);                                                \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) { v_[j] = lo[j]; v_[4 + j] = hi[j]; }                                \
+    _Pragma("unroll") for (int w = 1; w < NW; ++w) {                                                                   \
+      const f32x4 l2 = *(const f32x4*)(red + w * 16 * LDW), h2 = *(const f32x4*)(red + w * 16 * LDW + 4);              \
+      _Pragma("unroll") for (int j = 0; j < 4; ++j) { v_[j] += l2[j]; v_[4 + j] += h2[j]; }                            \
+    }                                                                                                                  \
+  }
 
 // ---- fragment reads ------------------------------------------------------------------------------------------------
 // KC: block b = 16 operand rows; returns the 8 reduction elements k = s*32 + 8*(lane>>4) .. +7 of row (lane&15)

@@ -24,7 +24,7 @@ Coverage (kernel x epilogue x activation x layout; acts = NONE, ReLU, GELU, GELU
     (grouped and dense), split-K pseudo-experts           dealt experts, canaries in [Nb, ldc), empty experts  test_dense_wgrad_contract
   every kernel, random data, Kd 1k..4k          NK, KN    PLAIN, fp64 bound of test_guards_gpu                test_random_data_bound[*]
   dot table vs kernel selector (kernel=2 / 4, M < 2048): refused before launching                            test_rowdot_kernel_selector
-  hipFuncSetAttribute per instantiation: ACCUM first on gg8 / gg4, then the others, in a fresh child          test_lds_attribute_per_instantiation
+  hipFuncSetAttribute per instantiation (common.h set_dyn_lds): ACCUM first on gg8 / gg4, then the others, in a fresh child   test_lds_attribute_per_instantiation
 
 Edges: expert rows 0, 1, 15, 16, 17, 127, 128, 129, 255, 256, 257, 256k + {64, 65, 192, 193}, an empty expert first and last; N a
 multiple of 8 but not of 128 (136, 264, 520); Kd a multiple of 8 but not of 64 (200, 520) except on gg4; lda > Kd (A's extra columns hold
@@ -702,7 +702,8 @@ print("ok")
 
 
 def test_lds_attribute_per_instantiation():
-    """hipFuncAttributeMaxDynamicSharedMemorySize is set per kernel instantiation: a fresh process launches EPI_ACCUM first on gg8_kernel
+    """hipFuncAttributeMaxDynamicSharedMemorySize is set per kernel instantiation (csrc/common.h set_dyn_lds, one flag per kernel): a fresh
+    process launches EPI_ACCUM first on gg8_kernel
     and gg4_kernel, then the other instantiations (and the 128-tile / weight-gradient kernels), and checks every result exactly."""
     r = _child(_LDS_CHILD, [], {})
     assert r.stdout.strip().endswith("ok")

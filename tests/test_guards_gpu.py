@@ -14,15 +14,15 @@ kernels write (the generic kernel refuses it before launching: a probe of which 
 
 Guard table (file:line at the time of writing -> inside / outside test):
 
-  csrc/gemm_bf16.hip:269 gg_fast_rowspace_ok   lda % 8                test_rowspace_lda[in] / [out]
+  csrc/gemm_bf16.hip:258 gg_fast_rowspace_ok   lda % 8                test_rowspace_lda[in] / [out]
                                                A alignment            test_rowspace_misaligned_a[in] / [out]
                                                ldb % 8                test_rowspace_ldb[in] / [out]
                                                M * lda * 2 < 2^31     test_rowspace_2gib_a[in] / [out]
                                                max(N,Kd) * ldb * 2    test_rowspace_2gib_b[in] / [out]
-  csrc/gemm_bf16.hip:301 gg_fast_wgrad_ok      M * max(lda,ldb) * 2   test_wgrad_2gib[in] / [out]
+  csrc/gemm_bf16.hip:285 gg_fast_wgrad_ok      M * max(lda,ldb) * 2   test_wgrad_2gib[in] / [out]
                                                A / B alignment        test_wgrad_misaligned[in] / [a] / [b]
   csrc/capi.hip:126 use_v2_rowspace            M, N, Kd               test_v2_rowspace_rule[*]
-  csrc/capi.hip:132 use_v4_rowspace (gg4_rowspace_ok, gemm_bf16_v4.hip:315)  test_v4_k_pair_rule[*]
+  csrc/capi.hip:132 use_v4_rowspace (gg4_rowspace_ok, gemm_bf16_v4.hip:279)  test_v4_k_pair_rule[*]
   csrc/capi.hip:150 use_v2_wgrad               Na, Nb, M              test_v2_wgrad_rule[*]
   csrc/gemm_generic.hip:162 row-tile limit     grid.y <= 65535        test_generic_row_tile_limit[in] / [out]
   csrc/capi.hip:186 gate_logits fast GEMM      w_gate alignment       test_dense_gemm_misaligned_b[in] / [out]

@@ -37,9 +37,10 @@ def pmc(path, name):
 
 def bench_name(k):
     """bench.py's profile label (ops._timed) of a grouped-GEMM kernel: operand layout for the bf16 kernels, the file for the others."""
-    if re.match(r'gg4_kernel<0>|gg8_kernel<0, 0,', k):
+    # demangled: gg8_kernel<ROWK, COLK, SCHED, ACC>, gg4_kernel<COLK, ACC>; COLK 0 = K-contiguous weights (NT), 1 = K-major (NN, gg8 only)
+    if re.match(r'gg4_kernel<0[,>]|gg8_kernel<0, 0,', k):
         return "grouped_gemm_nt"
-    if re.match(r'gg4_kernel<1>|gg8_kernel<0, 1,', k) or k == "gg8c_kernel":      # gg8c: fp32 master weights, K-major (ops.grouped_gemm_f32w)
+    if re.match(r'gg8_kernel<0, 1,', k) or k == "gg8c_kernel":      # gg8c: fp32 master weights, K-major (ops.grouped_gemm_f32w)
         return "grouped_gemm_nn"
     return {"gg8w_kernel": "grouped_wgrad_tn", "gg8f_kernel": "grouped_gemm_mxfp8"}.get(k)
 
