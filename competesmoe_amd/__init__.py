@@ -11,7 +11,8 @@ __all__ = ["_lib", "decode_rows"]
 def decode_rows(n=None) -> int:
     """Decode-path switch: `n` = the largest number of routed rows (T * K) a forward-only call may have to run its expert GEMMs on
     the weight-streaming kernel (csmoe_grouped_gemm_skinny; csmoe_grouped_gemm_skinny_mxfp8 in the fp8 layers with
-    `args.fp8_weight_cache`) without a dispatch copy; 0 (the default, or CSMOE_DECODE_ROWS unset) switches the path off.
+    `args.fp8_weight_cache`, or csmoe_grouped_gemm_skinny_mxfp4w on MXFP4 weight tables where such a layer also sets
+    `args.fp4_decode_weights`) without a dispatch copy; 0 (the default, or CSMOE_DECODE_ROWS unset) switches the path off.
     Returns the value in force; `decode_rows()` only reads it."""
     from . import ops
     return ops.decode_rows(n)

@@ -100,6 +100,10 @@ SIGNATURES = {
     "csmoe_grouped_gemm_skinny_mxfp8": (_i, [_p, _l, _p, _l, _p, _i, _p, _p, _l, _l, _p, _p, _i, _i, _i, _i, _p, _p, _l, _p, _p, _l, _l,
                                              _i, _i, _p]),
     "csmoe_grouped_gemm_skinny_mxfp8_ok": (_i, [_i, _i, _i, _l, _l, _l, _l, _l, _l, _l, _i, _i]),
+    "csmoe_quantize_mxfp4": (_i, [_p, _p, _i, _l, _i, _i, _i, _i, _p, _p, _p]),
+    "csmoe_grouped_gemm_skinny_mxfp4w": (_i, [_p, _l, _p, _l, _p, _i, _p, _p, _l, _l, _p, _p, _i, _i, _i, _i, _p, _p, _l, _p, _p, _l, _l,
+                                              _i, _i, _p]),
+    "csmoe_grouped_gemm_skinny_mxfp4w_ok": (_i, [_i, _i, _i, _l, _l, _l, _l, _l, _l, _l, _i, _i]),
     "csmoe_dense_gemm_mxfp8": (_i, [_p, _l, _p, _l, _p, _p, _l, _l, _p, _i, _i, _i, _p, _p, _p, _l, _i, _i, _p]),
     "csmoe_token_pad_bound": (_l, [_l, _i]),
     "csmoe_quantize_mxfp8_tokens": (_i, [_p, _l, _i, _i, _i, _p, _i, _l, _p, _p, _p, _p, _p, _p]),

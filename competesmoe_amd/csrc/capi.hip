@@ -62,6 +62,14 @@ int gg_skinny8_rowspace(const void* Aq, int64_t lda, const void* As, int64_t lda
                         const void* const* bq_ptrs, const void* const* bs_ptrs, int64_t ldb, int64_t ldbs,
                         const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2,
                         int64_t ldc, void* Cq, void* Cs, int64_t ldcq, int64_t ldcs, int epilogue, int act, hipStream_t st);
+int k_quantize_mxfp4(const void* const* x_ptrs, const void* x_single, int E, int64_t ldx, int R, int C, int in_dtype, int transpose,
+                     void* q, void* s, hipStream_t st);
+bool gg_skinny4w_shape_ok(int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc, int64_t ldcq, int64_t ldcs, int M, int N,
+                          int Kd, int quant_out);
+int gg_skinny4w_rowspace(const void* Aq, int64_t lda, const void* As, int64_t ldas, const int32_t* src_rows, int src_div,
+                         const void* const* bq_ptrs, const void* const* bs_ptrs, int64_t ldb, int64_t ldbs,
+                         const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2,
+                         int64_t ldc, void* Cq, void* Cs, int64_t ldcq, int64_t ldcs, int epilogue, int act, hipStream_t st);
 int k_router_select(const void*, int, int, int, int, int, int, float, float*, int32_t*, float*, hipStream_t);
 int k_router_select_bwd(const void*, int, int, int, int, int, int, float, const float*, const int32_t*, const float*, const float*,
                         const float*, void*, hipStream_t);
@@ -843,6 +851,67 @@ int csmoe_grouped_gemm_skinny_mxfp8(const void* Aq, int64_t lda, const void* As,
     return CSMOE_ERR_UNSUPPORTED;
   }
   return gg_skinny8_rowspace(Aq, lda, As, ldas, src_rows, src_div, bq_ptrs, bs_ptrs, ldb, ldbs, bias_ptrs, offsets, E, M, N, Kd, C, C2,
+                             ldc, Cq, Cs, ldcq, ldcs, epilogue, act, (hipStream_t)stream);
+}
+
+
+// ---- MXFP4 weights for the W4A8 decode path: the quantiser (fp8_quant.hip) and gemm_skinny_fp4.hip.  Same refusal rules as the
+// fp8 twins: CSMOE_ERR_UNSUPPORTED before any pointer is looked at and before anything is launched.
+int csmoe_quantize_mxfp4(const void* x, const void* const* x_ptrs, int E, int64_t ldx, int R, int C, int dtype, int transpose,
+                         void* q, void* s, csmoe_stream_t stream) {
+  CSMOE_CHECK_ARG(dtype_ok(dtype) && E >= 1 && R >= 0 && C >= 0, "quantize_mxfp4: bad arguments");
+  CSMOE_CHECK_ARG((x_ptrs != nullptr) || (x != nullptr && E == 1) || R == 0 || C == 0, "quantize_mxfp4: no input");
+  if (R == 0 || C == 0) return CSMOE_OK;
+  CSMOE_CHECK_ARG(q && s && ldx >= C, "quantize_mxfp4: null output or leading dimension too small");
+  const int es = dtype == CSMOE_BF16 ? 2 : 4;
+  if (transpose) {
+    if (R % 32 != 0) { csmoe_set_error("quantize_mxfp4: transposed form needs R %% 32 == 0 (R=%d)", R); return CSMOE_ERR_UNSUPPORTED; }
+  } else {
+    if (C % 32 != 0 || (ldx * es) % 16 != 0 || (x && ((uintptr_t)x & 15))) {
+      csmoe_set_error("quantize_mxfp4: needs C %% 32 == 0 and 16-byte aligned rows (C=%d ldx=%lld)", C, (long long)ldx);
+      return CSMOE_ERR_UNSUPPORTED;
+    }
+  }
+  if ((uintptr_t)q & 15) { csmoe_set_error("quantize_mxfp4: q must be 16-byte aligned (a block is one 16-byte store)"); return CSMOE_ERR_UNSUPPORTED; }
+  return k_quantize_mxfp4(x_ptrs, x, E, ldx, R, C, dtype, transpose, q, s, (hipStream_t)stream);
+}
+
+int csmoe_grouped_gemm_skinny_mxfp4w_ok(int M, int N, int Kd, int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc,
+                                       int64_t ldcq, int64_t ldcs, int epilogue, int quant_out) {
+  if (!skinny8_epilogue_ok(epilogue) || (quant_out && epilogue != CSMOE_EPI_BIAS_ACT)) return 0;
+  if (M < 0 || N <= 0 || Kd <= 0 || lda < Kd || ldb < Kd / 2 || ldc < N || ldas < Kd / 32 || ldbs < Kd / 32) return 0;
+  if (quant_out && (ldcq < N || ldcs < N / 32)) return 0;
+  return gg_skinny4w_shape_ok(lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, M, N, Kd, quant_out) ? 1 : 0;
+}
+
+int csmoe_grouped_gemm_skinny_mxfp4w(const void* Aq, int64_t lda, const void* As, int64_t ldas, const int32_t* src_rows, int src_div,
+                                    const void* const* bq_ptrs, const void* const* bs_ptrs, int64_t ldb, int64_t ldbs,
+                                    const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C,
+                                    void* C2, int64_t ldc, void* Cq, void* Cs, int64_t ldcq, int64_t ldcs, int epilogue, int act,
+                                    csmoe_stream_t stream) {
+  CSMOE_CHECK_ARG(epilogue >= 0 && epilogue <= CSMOE_EPI_ACCUM && act >= 0 && act <= 5, "grouped_gemm_skinny_mxfp4w: bad epilogue/act");
+  CSMOE_CHECK_ARG(!src_rows || src_div > 0, "grouped_gemm_skinny_mxfp4w: src_div = %d must be positive", src_div);
+  CSMOE_CHECK_ARG(!Cq == !Cs, "grouped_gemm_skinny_mxfp4w: the quantised output needs both Cq and Cs");
+  if (epilogue == CSMOE_EPI_ACCUM) return accum_unsupported("grouped_gemm_skinny_mxfp4w");
+  if (!skinny8_epilogue_ok(epilogue)) {
+    csmoe_set_error("grouped_gemm_skinny_mxfp4w: forward epilogues only (PLAIN, BIAS, BIAS_ACT), got %d", epilogue);
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  CSMOE_CHECK_ARG(!Cq || epilogue == CSMOE_EPI_BIAS_ACT, "grouped_gemm_skinny_mxfp4w: Cq / Cs go with the BIAS_ACT epilogue");
+  CSMOE_CHECK_ARG(E > 0 && M >= 0 && N > 0 && Kd > 0, "grouped_gemm_skinny_mxfp4w: bad shape E=%d M=%d N=%d Kd=%d", E, M, N, Kd);
+  CSMOE_CHECK_ARG(lda >= Kd && ldb >= Kd / 2 && ldc >= N && ldas >= Kd / 32 && ldbs >= Kd / 32 && (!Cq || (ldcq >= N && ldcs >= N / 32)),
+                  "grouped_gemm_skinny_mxfp4w: leading dimension too small");
+  CSMOE_CHECK_ARG(bq_ptrs && bs_ptrs && offsets, "grouped_gemm_skinny_mxfp4w: null pointer table / offsets");
+  if (M == 0) return CSMOE_OK;
+  CSMOE_CHECK_ARG(Aq && As && (C || (epilogue == CSMOE_EPI_BIAS_ACT && (C2 || Cq))), "grouped_gemm_skinny_mxfp4w: null pointer");
+  if (!gg_skinny4w_shape_ok(lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, M, N, Kd, Cq != nullptr) || ((uintptr_t)Aq & 15) ||
+      ((uintptr_t)As & 3) || ((uintptr_t)C & 15) || ((uintptr_t)C2 & 15) || ((uintptr_t)Cq & 7)) {
+    csmoe_set_error("grouped_gemm_skinny_mxfp4w: needs Kd %% 128 == 0, N %% 8 == 0 (N %% 32 == 0 with Cq), lda, ldb (bytes of a packed row) multiples of 16, "
+                    "ldas, ldbs of 4, ldc, ldcq of 8, 16-byte aligned operands (As: 4-byte) and panels under 2 GiB "
+                    "(csmoe_grouped_gemm_skinny_mxfp4w_ok); M=%d N=%d Kd=%d", M, N, Kd);
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  return gg_skinny4w_rowspace(Aq, lda, As, ldas, src_rows, src_div, bq_ptrs, bs_ptrs, ldb, ldbs, bias_ptrs, offsets, E, M, N, Kd, C, C2,
                              ldc, Cq, Cs, ldcq, ldcs, epilogue, act, (hipStream_t)stream);
 }
 

@@ -6,7 +6,8 @@
 //   transposed: x [R, C] -> q [C, R] u8, s [C, R/32] u8          (blocks along dim 0: the same weights for the transposed product)
 // Inputs bf16 or fp32 (the pretrain stack's fp32 master weights are quantised directly: no bf16 cast pass).
 // The scale-and-convert device code (e8m0_of_amax, inv_scale_of, sat448, pack4_e4m3) lives in mx_quant.h, shared with the fused
-// quantised output of gemm_skinny_fp8.hip.
+// quantised output of gemm_skinny_fp8.hip.  The MXFP4 weight quantiser (csmoe_quantize_mxfp4: e2m1 elements, two per byte, the same
+// e8m0 block scales with emax = 2) is the rows / transposed pair once more, at the end of the kernels.
 #include "mx_quant.h"
 #include <algorithm>
 #include <type_traits>
@@ -392,7 +393,90 @@ __global__ void __launch_bounds__(256) dispatch_quant_kernel(const bf16* x, cons
   }
 }
 
+// ---- MXFP4 weight tables (csmoe_quantize_mxfp4): quant_rows_kernel / quant_cols_kernel with e2m1 elements, two per byte -----------
+// A block's 32 elements are 16 bytes (element 2 j in the low nibble of byte j): one 16-byte store per block.  q rows are C / 2
+// (rows form) or R / 2 (transposed) bytes; the scales as for MXFP8.
+__device__ __forceinline__ int quant4_block(const float (&v)[32], u32x4& o) {
+  float amax = 0.f;
+#pragma unroll
+  for (int j = 0; j < 32; ++j) amax = fmaxf(amax, fabsf(v[j]));
+  const int sb = e8m0_of_amax_fp4(amax);
+  const float inv = inv_scale_of(sb);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = pack8_e2m1(v + 8 * j, inv);
+  return sb;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) quant4_rows_kernel(const void* const* x_ptrs, const T* x_single, int64_t ldx, int R, int C,
+                                                          uint8_t* q, uint8_t* s, int64_t q_mat, int64_t s_mat) {
+  const int e = blockIdx.y;
+  const T* x = x_ptrs ? (const T*)x_ptrs[e] : x_single;
+  uint8_t* qe = q + (int64_t)e * q_mat;
+  uint8_t* se = s + (int64_t)e * s_mat;
+  const int nb = C >> 5;
+  const int64_t total = (int64_t)R * nb;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int r = (int)(i / nb), b = (int)(i - (int64_t)r * nb);
+    float v[32];
+    load32<T>(x + (int64_t)r * ldx + b * 32, v);
+    u32x4 o;
+    const int sb = quant4_block(v, o);
+    *(u32x4*)(qe + ((int64_t)r * nb + b) * 16) = o;
+    se[(int64_t)r * nb + b] = (uint8_t)sb;
+  }
+}
+
+// transposed: one wave per 32-row x 64-column tile; lane = column, the 32 rows of the block sit in the lane's registers
+template <typename T>
+__global__ void __launch_bounds__(256) quant4_cols_kernel(const void* const* x_ptrs, const T* x_single, int64_t ldx, int R, int C,
+                                                          uint8_t* q, uint8_t* s, int64_t q_mat, int64_t s_mat) {
+  const int e = blockIdx.y;
+  const T* x = x_ptrs ? (const T*)x_ptrs[e] : x_single;
+  uint8_t* qe = q + (int64_t)e * q_mat;       // [C, R/2]
+  uint8_t* se = s + (int64_t)e * s_mat;       // [C, R/32]
+  const int lane = threadIdx.x & 63;
+  const int rb_n = R >> 5, cb_n = (C + 63) >> 6;
+  const int64_t tiles = (int64_t)rb_n * cb_n;
+  for (int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); t < tiles; t += (int64_t)gridDim.x * 4) {
+    const int rb = (int)(t / cb_n), cb = (int)(t - (int64_t)rb * cb_n);
+    const int c = cb * 64 + lane;
+    if (c >= C) continue;
+    float v[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) v[i] = (float)x[(int64_t)(rb * 32 + i) * ldx + c];
+    u32x4 o;
+    const int sb = quant4_block(v, o);
+    *(u32x4*)(qe + ((int64_t)c * rb_n + rb) * 16) = o;
+    se[(int64_t)c * rb_n + rb] = (uint8_t)sb;
+  }
+}
+
 }  // namespace
+
+int k_quantize_mxfp4(const void* const* x_ptrs, const void* x_single, int E, int64_t ldx, int R, int C, int in_dtype, int transpose,
+                     void* q, void* s, hipStream_t st) {
+  if (E <= 0 || R <= 0 || C <= 0) return CSMOE_OK;
+  const int64_t q_mat = (int64_t)R * C / 2;
+  const int64_t s_mat = transpose ? (int64_t)C * (R / 32) : (int64_t)R * (C / 32);
+  if (!transpose) {
+    const int64_t total = (int64_t)R * (C / 32);
+    dim3 grid((unsigned)std::min<int64_t>((total + 255) / 256, 8192), (unsigned)E), block(256);
+    if (in_dtype == CSMOE_BF16)
+      hipLaunchKernelGGL((quant4_rows_kernel<bf16>), grid, block, 0, st, x_ptrs, (const bf16*)x_single, ldx, R, C, (uint8_t*)q, (uint8_t*)s, q_mat, s_mat);
+    else
+      hipLaunchKernelGGL((quant4_rows_kernel<float>), grid, block, 0, st, x_ptrs, (const float*)x_single, ldx, R, C, (uint8_t*)q, (uint8_t*)s, q_mat, s_mat);
+  } else {
+    const int64_t tiles = (int64_t)(R / 32) * ((C + 63) / 64);
+    dim3 grid((unsigned)std::min<int64_t>((tiles + 3) / 4, 8192), (unsigned)E), block(256);
+    if (in_dtype == CSMOE_BF16)
+      hipLaunchKernelGGL((quant4_cols_kernel<bf16>), grid, block, 0, st, x_ptrs, (const bf16*)x_single, ldx, R, C, (uint8_t*)q, (uint8_t*)s, q_mat, s_mat);
+    else
+      hipLaunchKernelGGL((quant4_cols_kernel<float>), grid, block, 0, st, x_ptrs, (const float*)x_single, ldx, R, C, (uint8_t*)q, (uint8_t*)s, q_mat, s_mat);
+  }
+  CSMOE_CHECK_LAUNCH("quantize_mxfp4");
+  return CSMOE_OK;
+}
 
 int k_quantize_mxfp8_both(const void* const* x_ptrs, const void* x_single, int E, int64_t ldx, int R, int C, int in_dtype, void* q,
                           void* s, void* qt, void* st, hipStream_t stream) {

@@ -41,7 +41,8 @@
 //     host requires N % 32 == 0 and the slab is a multiple of 32 wide, so the four threads of a 32-column block are in one
 //     workgroup, adjacent, in one row, and all inside or all outside [0, N).
 //
-// Epilogue = the non-gradient branch of gemm_epilogue.h at the same rounding points as csmoe_grouped_gemm_mxfp8 (the product plus
+// Epilogue (gemm_skinny_mx_epilogue.inc, one copy for this kernel and gemm_skinny_fp4.hip; the argument block is gemm_skinny_mx.h's)
+// = the non-gradient branch of gemm_epilogue.h at the same rounding points as csmoe_grouped_gemm_mxfp8 (the product plus
 // bias is rounded to bf16, the activation sees the rounded value and is rounded again), 8 columns per thread through act_fwd8,
 // 16-byte stores.  Optional fused MXFP8 output (BIAS_ACT): Cq / Cs take the MX quantisation of the bf16-ROUNDED activated output,
 // blocks along N, byte for byte what csmoe_quantize_mxfp8(transpose = 0) writes for C2 (the scale-and-convert code is mx_quant.h's,
@@ -53,26 +54,9 @@
 //   <2>             107      0     74             18,432        0                         4
 //   <4>             126      0     74             34,816        0                         4
 // (a workgroup is 2 waves per SIMD: two workgroups are resident per CU.)
-#include "gemm_tiles.h"
-#include "mx_quant.h"
-#include <algorithm>
-
-using namespace ggt;
+#include "gemm_skinny_mx.h"
 
 namespace {
-
-constexpr int NW = 8;      // waves per workgroup (the K range of a tile is dealt to them)
-
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef __attribute__((address_space(1))) uint8_t gbyte;
-typedef __attribute__((address_space(1))) i32x4 gi32x4;
-
-struct Skinny8Args {
-  const uint8_t* A; int64_t lda; const uint8_t* AS; int64_t ldas; const int32_t* src_rows; int src_div;
-  const void* const* bq_ptrs; const void* const* bs_ptrs; int64_t ldb, ldbs; const void* const* bias_ptrs;
-  const int32_t* offsets; int E, M, N, Kd;
-  bf16* C; bf16* C2; int64_t ldc; uint8_t* Cq; uint8_t* Cs; int64_t ldcq, ldcs; int epilogue, act;
-};
 
 struct Frag8 { i32x4 lo, hi; int sc; };      // one row's 32 k-bytes of a K-step in the MFMA's k order, and its block's scale byte
 
@@ -84,7 +68,6 @@ template <int NB>
 __global__ void __launch_bounds__(NW * 64, 4) skinny8_kernel(Skinny8Args p) {
   constexpr int SLAB = 16 * NB;                       // output columns per workgroup
   constexpr int LDW = SLAB + 4;                       // floats per row of a wave's partial tile
-  constexpr int CPR = 2 * NB;                         // epilogue threads (8 columns each) per row
   constexpr int U = NB == 2 ? 3 : 2;                  // K-steps whose loads a wave issues before it waits for the first
   static_assert(NB == 2 || NB == 4, "a 32-column block of the quantised output lies inside one slab");
   __shared__ __attribute__((aligned(16))) float red_s[NW * 16 * LDW];
@@ -178,48 +161,7 @@ __global__ void __launch_bounds__(NW * 64, 4) skinny8_kernel(Skinny8Args p) {
   SKINNY_STORE_PARTIAL(red_s, acc);
 
   // ---------------- epilogue: thread (r, cg) owns 8 columns of one row; whole waves past the 16 rows leave ----------------
-  if (threadIdx.x >= 16 * CPR) return;
-  const int r = threadIdx.x / CPR, cg = threadIdx.x % CPR;
-  const int ncol = n0 + cg * 8;
-  const bool live = r < rows && ncol < p.N;           // the others stay for the shuffles only
-  SKINNY_SUM_PARTIALS(v, red_s, r, cg);
-  float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (p.epilogue != CSMOE_EPI_PLAIN && live) {
-    const void* bias = p.bias_ptrs ? p.bias_ptrs[e] : nullptr;
-    if (bias) {
-      const bf16x8 b8 = *(const bf16x8*)((const bf16*)bias + ncol);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) bv[j] = (float)b8[j];
-    }
-  }
-  const int64_t o = (int64_t)(row0 + r) * p.ldc + ncol;
-  bf16x8 o0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { o0[j] = (bf16)(v[j] + bv[j]); v[j] = (float)o0[j]; }
-  if (p.C && live) *(bf16x8*)(p.C + o) = o0;
-  if (p.epilogue != CSMOE_EPI_BIAS_ACT || !(p.C2 || p.Cq)) return;
-  act_fwd8(v, p.act);
-  bf16x8 o1;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) o1[j] = (bf16)v[j];
-  if (p.C2 && live) *(bf16x8*)(p.C2 + o) = o1;
-  if (p.Cq) {                                         // wave-uniform; every thread of the wave is still here
-    float f[8];
-    float amax = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { f[j] = (float)o1[j]; amax = fmaxf(amax, fabsf(f[j])); }
-    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-    amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-    const int sb = e8m0_of_amax(amax);
-    const float inv = inv_scale_of(sb);
-    u32x2 q;
-    q[0] = pack4_e4m3(f[0] * inv, f[1] * inv, f[2] * inv, f[3] * inv);
-    q[1] = pack4_e4m3(f[4] * inv, f[5] * inv, f[6] * inv, f[7] * inv);
-    if (live) {
-      *(u32x2*)(p.Cq + (int64_t)(row0 + r) * p.ldcq + ncol) = q;
-      if ((cg & 3) == 0) p.Cs[(int64_t)(row0 + r) * p.ldcs + (ncol >> 5)] = (uint8_t)sb;
-    }
-  }
+#include "gemm_skinny_mx_epilogue.inc"
 }
 
 }  // namespace

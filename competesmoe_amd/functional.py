@@ -1399,6 +1399,56 @@ def _ffn_fp8_decode(x2, w1, w2, b1, act: int, offsets, src_rows, src_div: int):
     return ops.grouped_gemm_skinny_mxfp8(hq, hs, vq, vs, offsets)
 
 
+# MXFP4 forward tables for the W4A8 decode path (`args.fp4_decode_weights`): a cache of their own, keyed like _FP8_WCACHE (storage
+# and version counter), so a decode-only process holds the 4-bit tables alone (0.516 of the fp8 forward tables) and never builds an
+# fp8 entry; a training call on the same parameters goes through _FP8_WCACHE as always.
+_FP4_WCACHE = {}
+
+
+def fp4_weight_cache_clear():
+    _FP4_WCACHE.clear()
+
+
+def _quantize_weight_fwd4(t: torch.Tensor):
+    """The MXFP4 forward table (q [.., C, R/2], s [.., C, R/32]) of a master weight tensor [.., R, C] (blocks along R, the forward
+    product's reduction dim), quantised once per parameter version."""
+    key = (t.data_ptr(), tuple(t.shape), t.dtype)
+    hit = _FP4_WCACHE.get(key)
+    if hit is not None and hit[0] == t._version:
+        return hit[1]
+    out = ops.quantize_mxfp4(t, transpose=True)
+    if hit is None:                                            # first entry under this key: it goes when its owner is freed
+        import weakref
+        owner = t._base if t._base is not None else t
+        weakref.finalize(owner, _FP4_WCACHE.pop, key, None)
+    _FP4_WCACHE[key] = (t._version, out)
+    return out
+
+
+def _fp4_decode_ok(n: int, D: int, F: int, Dout: int) -> bool:
+    """_fp8_decode_ok for csmoe_grouped_gemm_skinny_mxfp4w: both GEMMs of a forward-only call with n rows fit it."""
+    return (ops.grouped_gemm_skinny_mxfp4w_ok(n, F, D, epilogue=L.EPI_BIAS_ACT, quant_out=True)
+            and ops.grouped_gemm_skinny_mxfp4w_ok(n, Dout, F, epilogue=L.EPI_PLAIN))
+
+
+def _ffn_fp4_decode(x2, w1, w2, b1, act: int, offsets, src_rows, src_div: int):
+    """_ffn_fp8_decode with MXFP4 weight tables (W4A8, csrc/gemm_skinny_fp4.hip): the token rows are quantised to MXFP8 where they
+    lie, GEMM 1 gathers through `src_rows` and writes only the MXFP8 form of the activated output, GEMM 2 reads it; the weights are
+    the 4-bit forward tables of _quantize_weight_fwd4.  Same arguments and result."""
+    b1_ptrs = None
+    if b1 is not None:
+        b_op = b1.to(torch.bfloat16).contiguous()              # alive until GEMM 1 is enqueued
+        b1_ptrs = ops.ptr_table(b_op, b_op.numel() // b_op.shape[-1], b_op.shape[-1] * 2)
+    xq, xsc = ops.quantize_mxfp8(x2)
+    kq, ks = _quantize_weight_fwd4(w1)                         # [E, F, D/2], scales along D
+    vq, vs = _quantize_weight_fwd4(w2)                         # [E, Dout, F/2], scales along F
+    if kq.dim() == 2:
+        kq, ks, vq, vs = kq[None], ks[None], vq[None], vs[None]
+    _, _, hq, hs = ops.grouped_gemm_skinny_mxfp4w(xq, xsc, kq, ks, offsets, bias_ptrs=b1_ptrs, epilogue=L.EPI_BIAS_ACT, act=act,
+                                                  want_c=False, want_q=True, src_rows=src_rows, src_div=src_div)
+    return ops.grouped_gemm_skinny_mxfp4w(hq, hs, vq, vs, offsets)
+
+
 def _fp8_rows_and_weights(x2, w):
     """Checked inputs of the fp8 expert functions: contiguous bf16 rows, and the K weights as bf16 VALUES in fp32 (as in MoEFFNPacked;
     d w comes back unrounded)."""
@@ -1424,18 +1474,24 @@ class MoEFFNPackedFP8(_ForwardAware):
     and dy / dh quantised along the token dim inside every expert's rows (`csmoe_quantize_mxfp8_tokens`; dy and dh in the same pass
     as their row orientation); everything else the backward returns is unchanged, bit for bit.  Master weights (fp32 or bf16) are quantised directly, once per use and orientation -- there is no
     bf16 operand copy -- or, with `cache`, once per parameter version (_quantize_weight_both).  A call that needs no backward, with
-    `cache` and at most ops.decode_rows() routed rows, takes the decode path (_ffn_fp8_decode).  No counterpart upstream (the
+    `cache` and at most ops.decode_rows() routed rows, takes the decode path (_ffn_fp8_decode; with `fp4_decode` the W4A8 form
+    _ffn_fp4_decode on MXFP4 weight tables).  No counterpart upstream (the
     reference has no fp8): checked against oracle/mxfp8.py, tests/test_fp8_gpu.py, tests/test_decode_fp8_path_gpu.py."""
 
     @staticmethod
-    def forward(ctx, x2, w, idx, keys, values, bias, act: int, combine_mode: int, cache: bool = False, wgrad_fp8: bool = False):
+    def forward(ctx, x2, w, idx, keys, values, bias, act: int, combine_mode: int, cache: bool = False, wgrad_fp8: bool = False,
+                fp4_decode: bool = False):
         x2, w = _fp8_rows_and_weights(x2, w)
         E, D, F = keys.shape
         T = x2.shape[0]
         bins = ops.bin_tokens(idx, E)
         if (not _needs_backward(ctx) and cache and 0 < bins.n <= ops.decode_rows()
                 and _fp8_decode_ok(bins.n, D, F, values.shape[2])):
-            y = _ffn_fp8_decode(x2, keys, values, bias, act, bins.offsets, bins.perm, bins.K)
+            # `fp4_decode` (args.fp4_decode_weights): the same call on MXFP4 weight tables, where the fp8 decode path would run
+            if fp4_decode and _fp4_decode_ok(bins.n, D, F, values.shape[2]):
+                y = _ffn_fp4_decode(x2, keys, values, bias, act, bins.offsets, bins.perm, bins.K)
+            else:
+                y = _ffn_fp8_decode(x2, keys, values, bias, act, bins.offsets, bins.perm, bins.K)
             ctx.saved = None                     # no backward can follow
             return ops.combine(y, bins, idx, w, combine_mode, T)
         xs, xq, xsc = ops.dispatch_tokens_mxfp8(x2, bins)       # the gather and the quantiser in one pass (CSMOE_DISPATCH_QUANT=0: two)
@@ -1503,7 +1559,7 @@ class MoEFFNPackedFP8(_ForwardAware):
                 dhq, dhs = ops.quantize_mxfp8(dh)
             dxs = ops.grouped_gemm_mxfp8(dhq, dhs, kq, ks, bins.offsets)   # keys as stored: dxs = dh @ keys[e]^T
             dx2 = ops.dispatch_rows_bwd(dxs, bins, T)
-        return dx2, dw, None, gk, gv, gb, None, None, None, None
+        return dx2, dw, None, gk, gv, gb, None, None, None, None, None
 
 
 class DenseFFNFP8(_ForwardAware):
@@ -1512,12 +1568,13 @@ class DenseFFNFP8(_ForwardAware):
     pipe as in MoEFFNPackedFP8 (one expert: E = 1)."""
 
     @staticmethod
-    def forward(ctx, x2, w1, b1, w2, act: int, cache: bool = False, wgrad_fp8: bool = False):
+    def forward(ctx, x2, w1, b1, w2, act: int, cache: bool = False, wgrad_fp8: bool = False, fp4_decode: bool = False):
         T, D = x2.shape
         if (not _needs_backward(ctx) and cache and 0 < T <= ops.decode_rows() and x2.dtype == torch.bfloat16):
             x2 = x2.contiguous()
             if _fp8_decode_ok(T, D, w1.shape[1], w2.shape[1]):         # the decode path of MoEFFNPackedFP8 with E = 1
-                return _ffn_fp8_decode(x2, w1, w2, b1, act, ops.dense_offsets(T, x2.device), None, 1)
+                ffn = _ffn_fp4_decode if fp4_decode and _fp4_decode_ok(T, D, w1.shape[1], w2.shape[1]) else _ffn_fp8_decode
+                return ffn(x2, w1, w2, b1, act, ops.dense_offsets(T, x2.device), None, 1)
         y, saved, ctx.cfg = dense_ffn_fp8_forward(x2, w1, b1, w2, act, cache)
         ctx.save_for_backward(*saved)
         ctx.wgrad_fp8 = bool(wgrad_fp8)
@@ -1526,7 +1583,7 @@ class DenseFFNFP8(_ForwardAware):
     @staticmethod
     def backward(ctx, dy):
         dx, gw1, gb1, gw2 = dense_ffn_fp8_backward(ctx.saved_tensors, ctx.cfg, dy, ctx.needs_input_grad[:4], ctx.wgrad_fp8)
-        return dx, gw1, gb1, gw2, None, None, None
+        return dx, gw1, gb1, gw2, None, None, None, None
 
 
 def dense_ffn_fp8_forward(x2, w1, b1, w2, act: int, cache: bool):

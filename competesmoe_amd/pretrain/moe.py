@@ -97,6 +97,12 @@ class MoE(LoggingLayer, RegularizedLayer, OncePerIterLayer, nn.Module):
         self.fp8_wgrad = bool(getattr(args, "fp8_wgrad", _FP8_WGRAD_ENV))
         if self.fp8_wgrad and not self.fp8_experts:
             raise ValueError("competesmoe_amd: args.fp8_wgrad (or CSMOE_FP8_WGRAD=1) needs args.fp8_experts")
+        # W4A8 decode: where the fp8 decode path would run (forward-only, fp8_weight_cache, at most decode_rows() routed rows), the
+        # expert weights are MXFP4 tables (functional._ffn_fp4_decode); every other call is unchanged.  Off by default
+        self.fp4_decode_weights = bool(getattr(args, "fp4_decode_weights", False))
+        if self.fp4_decode_weights and not self.fp8_experts:
+            raise ValueError("competesmoe_amd: args.fp4_decode_weights is the 4-bit weight form of the fp8 decode path: it needs "
+                             "args.fp8_experts (and args.fp8_weight_cache to take effect)")
         self.selection_dropout = selection_dropout
         self.expert_dropout = expert_dropout
         self.sel_weight_scale = weight_scale
@@ -242,7 +248,8 @@ class MoE(LoggingLayer, RegularizedLayer, OncePerIterLayer, nn.Module):
             out = MoEFFNPackedFP8.apply(x2, wk.float().contiguous(), selected_experts.reshape(-1, K).int().contiguous(),
                                         self.keys if keys is None else keys, self.values if values is None else values,
                                         self.bias if bias is None else bias, self.act_code, L.COMBINE_DOT,
-                                        self.fp8_weight_cache and keys is None and values is None, self.fp8_wgrad)
+                                        self.fp8_weight_cache and keys is None and values is None, self.fp8_wgrad,
+                                        self.fp4_decode_weights)
             if res is not None:
                 out = res + out.view(res.shape)
             return out.view(*shp[:-1], -1)
@@ -274,7 +281,7 @@ class MoE(LoggingLayer, RegularizedLayer, OncePerIterLayer, nn.Module):
         b = None if bias_shared is None else bias_shared[0]
         if self.fp8_experts:
             y = DenseFFNFP8.apply(self.operand(x), keys_shared[0], b, values_shared[0], self.act_code, self.fp8_weight_cache,
-                                  self.fp8_wgrad)
+                                  self.fp8_wgrad, self.fp4_decode_weights)
             return y.view(*shp[:-1], -1)
         y = DenseFFN.apply(self.operand(x), keys_shared[0], b, values_shared[0], None, self.act_code, L.B_KN, True)
         return y.view(*shp[:-1], -1)

@@ -501,6 +501,39 @@ int csmoe_grouped_gemm_skinny_mxfp8(const void* Aq, int64_t lda, const void* As,
 int csmoe_grouped_gemm_skinny_mxfp8_ok(int M, int N, int Kd, int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc,
                                        int64_t ldcq, int64_t ldcs, int epilogue, int quant_out);
 
+/* ---- MXFP4 weights for decode (W4A8): a weight-only 4-bit form of the two entries above ------------------------------------
+ * Format (OCP Microscaling v1.0, MXFP4): blocks of 32 consecutive elements along the reduction dimension share one e8m0 scale byte
+ * s worth 2^(s - 127); elements are e2m1 (sign and magnitude, magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6); the shared exponent is
+ * floor(log2(amax)) - 2, the byte clamped to [0, 254]; an element is round-to-nearest-even of x * 2^-shared on that grid, saturated
+ * at +-6.  A row of Kd elements is Kd / 2 bytes in natural k order: byte j holds element 2 j in its low nibble and element 2 j + 1
+ * in its high nibble.  Non-finite inputs are outside the contract: +-inf becomes +-6 and a NaN +-0 (its sign bit), and their block
+ * takes the scale byte 253; nothing is read or written out of range because of them.
+ *
+ * csmoe_quantize_mxfp4: the argument list of csmoe_quantize_mxfp8.  transpose == 0: q [E, R, C/2], s [E, R, C/32] (blocks along C;
+ * C % 32 == 0, 16-byte aligned rows).  transpose != 0: q [E, C, R/2], s [E, C, R/32] (blocks along R; R % 32 == 0) -- the forward
+ * table of a master stored [Kd, N].  q 16-byte aligned (a block is one 16-byte store); else CSMOE_ERR_UNSUPPORTED. */
+int csmoe_quantize_mxfp4(const void* x, const void* const* x_ptrs, int E, int64_t ldx, int R, int C, int dtype, int transpose,
+                         void* q, void* s, csmoe_stream_t stream);
+/* csmoe_grouped_gemm_skinny_mxfp8 with MXFP4 weights (csrc/gemm_skinny_fp4.hip): the same decomposition, gather (src_rows /
+ * src_div for elements and scale rows), epilogues (PLAIN, BIAS, BIAS_ACT at the same rounding points) and optional fused MXFP8
+ * output Cq / Cs (byte for byte what csmoe_quantize_mxfp8 (transpose = 0) writes for C2).  For every expert e and binned row m
+ *     C[m, 0:N] = epilogue( sum_k dq(A)[row(m), k] dq(B_e)[n, k] ),   row(m) = src_rows ? src_rows[m] / src_div : m
+ * A = Aq [R, Kd] e4m3 (lda) with scales As [R, Kd/32] (ldas) exactly as above: the activations stay MXFP8.  B_e = bq_ptrs[e]
+ * [N, Kd/2] packed e2m1 with ldb counted in BYTES of the packed row (ldb >= Kd / 2), scales bs_ptrs[e] [N, Kd/32] (ldbs); every
+ * bq_ptrs[e] 16-byte and every bs_ptrs[e] 4-byte aligned (device tables: the caller's contract).
+ * Shape rule (csmoe_grouped_gemm_skinny_mxfp4w_ok): Kd % 128 == 0, N % 8 == 0, lda % 16 == 0, ldb % 16 == 0, ldas % 4 == 0,
+ * ldbs % 4 == 0, ldc % 8 == 0; with the quantised output N % 32 == 0 and ldcq % 8 == 0; Aq / C / C2 16-byte, Cq 8-byte and As 4-byte
+ * aligned; M * lda and N * ldb under 2 GiB.  Returns as the fp8 entry does: CSMOE_ERR_INVALID for bad arguments,
+ * CSMOE_ERR_UNSUPPORTED for a backward epilogue, CSMOE_EPI_ACCUM or a shape the rule rejects -- decided before any pointer is read
+ * and before anything is launched; M == 0 is CSMOE_OK.  No atomics, bit-identical from run to run. */
+int csmoe_grouped_gemm_skinny_mxfp4w(const void* Aq, int64_t lda, const void* As, int64_t ldas, const int32_t* src_rows, int src_div,
+                                     const void* const* bq_ptrs, const void* const* bs_ptrs, int64_t ldb, int64_t ldbs,
+                                     const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C,
+                                     void* C2, int64_t ldc, void* Cq, void* Cs, int64_t ldcq, int64_t ldcs, int epilogue, int act,
+                                     csmoe_stream_t stream);
+int csmoe_grouped_gemm_skinny_mxfp4w_ok(int M, int N, int Kd, int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc,
+                                        int64_t ldcq, int64_t ldcs, int epilogue, int quant_out);
+
 /* ---- MXFP8 weight gradients: operands quantised along the TOKEN dimension -------------------------------------------------
  * Blocking contract.  A block is 32 consecutive BINNED rows of ONE expert.  Binned order is that of csmoe_bin_tokens (a stable
  * counting sort: ascending t * K + k inside an expert -- the order `(idx == e).nonzero()` lists).  Expert e's count_e rows

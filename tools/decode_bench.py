@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Decode-time expert GEMMs: the weight-streaming kernel (csmoe_grouped_gemm_skinny, gather folded into the first product) against
 the same two products through csmoe_grouped_gemm(kernel=AUTO) behind a dispatch_tokens copy -- what a layer call does without
-the decode switch.  usage: python tools/decode_bench.py [--reps 30] [--out table.md] [--dtype bf16|fp8]
+the decode switch.  usage: python tools/decode_bench.py [--reps 30] [--out table.md] [--dtype bf16|fp8|fp4]
 
 Grid: T in {1 .. 256} tokens, K = 2, at the headline dimensions (D 4096, F 11008, 64 experts) and at the SigLIP layer's (1152 / 4304,
 4 experts), both weight layouts (B_NK with GELU as the LLaVA stack runs it, B_KN with ReLU as the pretrain stack does).  Both paths
@@ -19,7 +19,13 @@ are timed the same way, each in its own series of one process: the fp8 decode ch
 csmoe_grouped_gemm_skinny_mxfp8 launches, the first gathering and writing the MXFP8 hidden activations), the tiled fp8 chain the
 layer runs without the switch (dispatch_tokens_mxfp8 + grouped_gemm_mxfp8 + quantize_mxfp8 + grouped_gemm_mxfp8), and the bf16
 decode chain at the same dimensions (B_KN, ReLU: the pretrain stack).  `+-` is half the interquartile range of the repetitions;
-the fp8 weight traffic counts one byte per element plus the scale bytes (1 / 32)."""
+the fp8 weight traffic counts one byte per element plus the scale bytes (1 / 32).
+
+--dtype fp4 (`args.fp4_decode_weights`): the W4A8 decode chain (quantize_mxfp8 of the T rows + two csmoe_grouped_gemm_skinny_mxfp4w
+launches on MXFP4 weight tables) beside the fp8 decode chain above, in the same process and rotation (the order of the two
+alternates with the repetition; cold, each chain reads its own copies, at least three of them).  The fp4 weight traffic counts
+half a byte per element plus the scale bytes: 0.516 of the fp8 table, the bound of the ratio.  The last columns are the bytes the
+two weight caches of a layer of these dimensions hold (both tables of all E experts, forward orientation)."""
 import argparse
 import os
 import statistics
@@ -188,22 +194,95 @@ def main_fp8(a):
     return lines
 
 
+def weight_sets_fp4(D, F, E):
+    """Copies of the two MXFP4 forward tables ([E, F, D / 2] / [E, D, F / 2] packed e2m1, scales [.., / 32]): every byte is two
+    finite elements."""
+    one = E * D * F
+    n = max(3, min(12, -(-(3 * 256 << 20) // one)))
+
+    def mk(rows, cols):
+        return (torch.randint(0, 256, (E, rows, cols // 2), device=DEV, dtype=torch.uint8),
+                torch.randint(112, 118, (E, rows, cols // 32), device=DEV, dtype=torch.uint8))
+    return [(mk(F, D), mk(D, F)) for _ in range(n)]
+
+
+def bench_case_fp4(sets4, sets8, D, F, E, T, reps, warm):
+    """(median ms, spread) of the fp4 (W4A8) decode chain and the fp8 decode chain, and the active experts."""
+    g = torch.Generator().manual_seed(1000 * T + 4)
+    x = torch.randn(T, D, generator=g).bfloat16().to(DEV)
+    routes = []
+    for r in range(reps + 5):
+        idx = torch.rand(T, E, generator=g).topk(K, -1).indices.int()
+        if warm and routes:
+            idx = routes[0][0].cpu()
+        active = int(idx.unique().numel())
+        idx = idx.to(DEV)
+        routes.append((idx, ops.bin_tokens(idx, E), active))
+
+    def chain(gemm):
+        def run(bins, t):
+            (kq, ks), (vq, vs) = t
+            xq, xs = ops.quantize_mxfp8(x)
+            _, _, hq, hs = gemm(xq, xs, kq, ks, bins.offsets, epilogue=L.EPI_BIAS_ACT, act=L.ACT_RELU, want_c=False, want_q=True,
+                                src_rows=bins.perm, src_div=K)
+            gemm(hq, hs, vq, vs, bins.offsets)
+        return run
+
+    chains = (("fp4", chain(ops.grouped_gemm_skinny_mxfp4w), sets4), ("fp8", chain(ops.grouped_gemm_skinny_mxfp8), sets8))
+    ev = {c[0]: [] for c in chains}
+    for r, (idx, bins, active) in enumerate(routes):
+        for j in range(2):
+            name, fn, pool = chains[(r + j) % 2]
+            t = pool[0] if warm else pool[r % len(pool)]     # cold: a copy's next use comes after the other copies' and chain's traffic
+            e = timed(lambda: fn(bins, t))
+            if r >= 5:
+                ev[name].append(e)
+    torch.cuda.synchronize()
+    return {k: _med_spread(v) for k, v in ev.items()}, statistics.median(a for _, _, a in routes[5:])
+
+
+def main_fp4(a):
+    lines = [f"device: {torch.cuda.get_device_name(0)}; reps {a.reps}, median +- half the interquartile range; K = {K}; ReLU", "",
+             "| dims | T | rows | cold fp4 decode ms | cold fp8 decode ms | fp8/fp4 | wins by more than both spreads | fp4 GB | fp4 GB/s | "
+             "% of 8.0 TB/s | fp8 GB | fp8 GB/s | % of 8.0 TB/s | warm fp4 ms | warm fp8 ms | warm fp8/fp4 | fp4 cache GB | fp8 cache GB |",
+             "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for name in a.dims.split(","):
+        D, F, E = DIMS[name]
+        sets4, sets8 = weight_sets_fp4(D, F, E), weight_sets_fp8(D, F, E)
+        c4, c8 = E * 2 * D * F * (0.5 + 1 / 32), E * 2 * D * F * (1 + 1 / 32)
+        for T in TS:
+            cold, active = bench_case_fp4(sets4, sets8, D, F, E, T, a.reps, warm=False)
+            warm, _ = bench_case_fp4(sets4, sets8, D, F, E, T, a.reps, warm=True)
+            b4, b8 = active * 2 * D * F * (0.5 + 1 / 32), active * 2 * D * F * (1 + 1 / 32)
+            (n4, s4), (n8, s8) = cold["fp4"], cold["fp8"]
+            (w4, ws4), (w8, ws8) = warm["fp4"], warm["fp8"]
+            bw4, bw8 = b4 / (n4 * 1e-3), b8 / (n8 * 1e-3)
+            verdict = "fp4" if n8 - n4 > s4 + s8 else ("fp8" if n4 - n8 > s4 + s8 else "neither")
+            lines.append(f"| {name} | {T} | {T * K} | {n4:.4f} +- {s4:.4f} | {n8:.4f} +- {s8:.4f} | {n8 / n4:.2f} | {verdict} | {b4 / 1e9:.3f} | "
+                         f"{bw4 / 1e9:.0f} | {100 * bw4 / HBM_PEAK:.1f} | {b8 / 1e9:.3f} | {bw8 / 1e9:.0f} | {100 * bw8 / HBM_PEAK:.1f} | "
+                         f"{w4:.4f} +- {ws4:.4f} | {w8:.4f} +- {ws8:.4f} | {w8 / w4:.2f} | {c4 / 1e9:.2f} | {c8 / 1e9:.2f} |")
+            print(lines[-1], flush=True)
+        del sets4, sets8
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--dims", default=None, help="default: headline,siglip (bf16) / headline,config5 (fp8)")
-    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--dims", default=None, help="default: headline,siglip (bf16) / headline,config5 (fp8, fp4)")
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "fp4"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    a.dims = a.dims or ("headline,config5" if a.dtype == "fp8" else "headline,siglip")
+    a.dims = a.dims or ("headline,config5" if a.dtype != "bf16" else "headline,siglip")
     for name in a.dims.split(","):
         if name not in DIMS:
             ap.error(f"unknown dims '{name}'; choose from {', '.join(DIMS)}")
         D, F, _ = DIMS[name]
-        if a.dtype == "fp8" and (D % 128 or F % 128):
-            ap.error(f"--dtype fp8: dims '{name}' (D = {D}, F = {F}) are no multiples of 128, which the MXFP8 kernels need for both "
+        if a.dtype != "bf16" and (D % 128 or F % 128):
+            ap.error(f"--dtype {a.dtype}: dims '{name}' (D = {D}, F = {F}) are no multiples of 128, which the MXFP8 kernels need for both "
                      "reduction dims; choose from headline, config5")
-    lines = main_fp8(a) if a.dtype == "fp8" else main_bf16(a)
+    lines = {"fp8": main_fp8, "fp4": main_fp4, "bf16": main_bf16}[a.dtype](a)
     text = "\n".join(lines) + "\n"
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
