@@ -105,6 +105,9 @@ SIGNATURES = {
                                               _i, _i, _p]),
     "csmoe_grouped_gemm_skinny_mxfp4w_ok": (_i, [_i, _i, _i, _l, _l, _l, _l, _l, _l, _l, _i, _i]),
     "csmoe_dense_gemm_mxfp8": (_i, [_p, _l, _p, _l, _p, _p, _l, _l, _p, _i, _i, _i, _p, _p, _p, _l, _i, _i, _p]),
+    "csmoe_grouped_gemm_mxfp8_q": (_i, [_p, _l, _p, _l, _p, _p, _l, _l, _p, _p, _i, _i, _i, _i, _p, _p, _p, _l, _i, _i, _p, _l, _p, _l, _p]),
+    "csmoe_dense_gemm_mxfp8_q": (_i, [_p, _l, _p, _l, _p, _p, _l, _l, _p, _i, _i, _i, _p, _p, _p, _l, _i, _i, _p, _l, _p, _l, _p]),
+    "csmoe_gemm_mxfp8_q_ok": (_i, [_i, _i, _i, _l, _l, _l, _l, _l, _l, _l, _i, _i, _i]),
     "csmoe_token_pad_bound": (_l, [_l, _i]),
     "csmoe_quantize_mxfp8_tokens": (_i, [_p, _l, _i, _i, _i, _p, _i, _l, _p, _p, _p, _p, _p, _p]),
     "csmoe_grouped_wgrad_mxfp8": (_i, [_p, _l, _p, _l, _p, _l, _p, _l, _p, _i, _l, _i, _i, _p, _l, _i, _i, _p, _p]),

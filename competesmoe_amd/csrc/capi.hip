@@ -51,6 +51,10 @@ int gg8f_rowspace(const void* Aq, int64_t lda, const void* As, int64_t ldas, con
                   int64_t ldb, int64_t ldbs, const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd,
                   void* C, void* C2, const void* aux, int64_t ldc, int epilogue, int act, const void* single_B,
                   const void* single_BS, const void* single_bias, hipStream_t st);
+int gg8f_rowspace_q(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* const* bq_ptrs, const void* const* bs_ptrs,
+                    int64_t ldb, int64_t ldbs, const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd,
+                    void* C, void* C2, int64_t ldc, void* Cq, int64_t ldcq, void* Cs, int64_t ldcs, int act, const void* single_B,
+                    const void* single_BS, const void* single_bias, hipStream_t st);
 int k_quantize_mxfp8_tokens(const void* x, int64_t ldx, const int32_t* offsets, int E, int C, int64_t n_pad, void* poff, void* q, void* s,
                             void* qt, void* st, hipStream_t stream);
 int gg8f_wgrad(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Bq, int64_t ldb, const void* Bs, int64_t ldbs,
@@ -804,6 +808,102 @@ int csmoe_dense_gemm_mxfp8(const void* Aq, int64_t lda, const void* As, int64_t 
   CSMOE_CHECK_ARG(M == 0 || epilogue != CSMOE_EPI_ACTGRAD || aux, "dense_gemm_mxfp8: ACTGRAD epilogue needs aux");
   if (M == 0) return CSMOE_OK;
   if (int rc = fp8_shape_ok(lda, ldas, ldb, ldbs, ldc, N, Kd, Aq, C ? C : C2, "dense_gemm_mxfp8")) return rc;
+  return gg8f_rowspace(Aq, lda, As, ldas, nullptr, nullptr, ldb, ldbs, nullptr, nullptr, 1, M, N, Kd, C, C2, aux, ldc, epilogue, act,
+                       Bq, Bs, bias, (hipStream_t)stream);
+}
+
+
+// ---- the tiled MXFP8 GEMM with a quantised activated output (gg8fq_kernel, gemm_epilogue_q.h) and, on the dense entry, the two
+// affinity epilogues of the competition pass.  The entries above keep their signatures and refusals; these add Cq / Cs.  Every
+// refusal is decided from the argument VALUES, before any pointer is read and before anything is launched.
+static bool fp8_q_epilogue_ok(int epilogue, int dense) {
+  return (epilogue >= CSMOE_EPI_PLAIN && epilogue <= CSMOE_EPI_ACTGRAD) ||
+         (dense && (epilogue == CSMOE_EPI_SOFTPLUS_ROWSUM || epilogue == CSMOE_EPI_SOFTPLUS_GRAD));
+}
+// the shape rule of both entries; ldc of a SOFTPLUS_ROWSUM launch is the row stride of its FP32 table [M, ceil(N / 256)]
+static bool fp8_q_shape_ok(int M, int N, int Kd, int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc, int64_t ldcq,
+                           int64_t ldcs, int epilogue, int quant_out) {
+  if (M < 0 || N <= 0 || Kd <= 0 || lda < Kd || ldb < Kd || ldas < Kd / 32 || ldbs < Kd / 32) return false;
+  if (Kd % 128 != 0 || N % 8 != 0 || lda % 16 != 0 || ldb % 16 != 0 || ldas % 4 != 0 || ldbs % 4 != 0) return false;
+  if (epilogue == CSMOE_EPI_SOFTPLUS_ROWSUM) {
+    if (ldc < (N + 255) / 256) return false;
+  } else if (ldc < N || ldc % 8 != 0) {
+    return false;
+  }
+  if (quant_out && (epilogue != CSMOE_EPI_BIAS_ACT || N % 32 != 0 || ldcq < N || ldcq % 16 != 0 || ldcs < N / 32)) return false;
+  return true;
+}
+
+int csmoe_gemm_mxfp8_q_ok(int M, int N, int Kd, int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc, int64_t ldcq,
+                          int64_t ldcs, int epilogue, int quant_out, int dense) {
+  if (!fp8_q_epilogue_ok(epilogue, dense)) return 0;
+  return fp8_q_shape_ok(M, N, Kd, lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, epilogue, quant_out) ? 1 : 0;
+}
+
+// shared by the two entries: returns CSMOE_OK when the launch may go ahead
+static int fp8_q_args(const char* who, int dense, int E, int M, int N, int Kd, int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs,
+                      const void* Aq, const void* As, const void* C, const void* C2, const void* aux, int64_t ldc, const void* Cq,
+                      int64_t ldcq, const void* Cs, int64_t ldcs, int epilogue, int act) {
+  CSMOE_CHECK_ARG(E > 0 && M >= 0 && N > 0 && Kd > 0, "%s: bad shape E=%d M=%d N=%d Kd=%d", who, E, M, N, Kd);
+  if (epilogue == CSMOE_EPI_ACCUM) return accum_unsupported(who);
+  const bool softplus = epilogue == CSMOE_EPI_SOFTPLUS_ROWSUM || epilogue == CSMOE_EPI_SOFTPLUS_GRAD;
+  // act: an activation code, or the flag bits of the affinity epilogues (bit 0 precise, bit 1 rounded)
+  CSMOE_CHECK_ARG(fp8_q_epilogue_ok(epilogue, dense) && act >= 0 && act <= (softplus ? 3 : 5), "%s: bad epilogue/act (%d, %d)", who,
+                  epilogue, act);
+  CSMOE_CHECK_ARG(!Cq == !Cs, "%s: the quantised output needs both Cq and Cs", who);
+  CSMOE_CHECK_ARG(!Cq || epilogue == CSMOE_EPI_BIAS_ACT, "%s: Cq / Cs go with the BIAS_ACT epilogue", who);
+  CSMOE_CHECK_ARG(epilogue != CSMOE_EPI_SOFTPLUS_GRAD || aux, "%s: SOFTPLUS_GRAD needs aux (the FP32 row scales)", who);
+  CSMOE_CHECK_ARG(M == 0 || epilogue != CSMOE_EPI_ACTGRAD || aux, "%s: ACTGRAD epilogue needs aux", who);
+  CSMOE_CHECK_ARG(lda >= Kd && ldb >= Kd && ldas >= Kd / 32 && ldbs >= Kd / 32 &&
+                  ldc >= (epilogue == CSMOE_EPI_SOFTPLUS_ROWSUM ? (N + 255) / 256 : N) && (!Cq || (ldcq >= N && ldcs >= N / 32)),
+                  "%s: leading dimension too small (SOFTPLUS_ROWSUM: ldc is the row stride of the FP32 table [M, ceil(N/256)])", who);
+  if (Cq && N % 32 != 0) {
+    csmoe_set_error("%s: Cq / Cs need N %% 32 == 0, so that no 32-element block straddles the matrix edge (N=%d)", who, N);
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  if (Cq && (((uintptr_t)Cq & 15) || ldcq % 16 != 0)) {
+    csmoe_set_error("%s: Cq must be 16-byte aligned with ldcq %% 16 == 0 (ldcq=%lld)", who, (long long)ldcq);
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  if (!fp8_q_shape_ok(M, N, Kd, lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, epilogue, Cq != nullptr) ||
+      (((uintptr_t)Aq | (uintptr_t)C | (uintptr_t)C2) & 15) || ((uintptr_t)As & 3) || ((uintptr_t)aux & (softplus ? 3 : 15))) {
+    csmoe_set_error("%s: needs Kd %% 128 == 0, N %% 8 == 0, lda, ldb multiples of 16, ldas, ldbs of 4, ldc of 8, 16-byte aligned "
+                    "operands (csmoe_gemm_mxfp8_q_ok); N=%d Kd=%d", who, N, Kd);
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  CSMOE_CHECK_ARG(M == 0 || (Aq && As && (C || (epilogue == CSMOE_EPI_BIAS_ACT && (C2 || Cq)))), "%s: null pointer", who);
+  return CSMOE_OK;
+}
+
+int csmoe_grouped_gemm_mxfp8_q(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* const* bq_ptrs,
+                               const void* const* bs_ptrs, int64_t ldb, int64_t ldbs, const void* const* bias_ptrs,
+                               const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2, const void* aux, int64_t ldc,
+                               int epilogue, int act, void* Cq, int64_t ldcq, void* Cs, int64_t ldcs, csmoe_stream_t stream) {
+  if (int rc = fp8_q_args("grouped_gemm_mxfp8_q", 0, E, M, N, Kd, lda, ldas, ldb, ldbs, Aq, As, C, C2, aux, ldc, Cq, ldcq, Cs, ldcs,
+                          epilogue, act)) return rc;
+  CSMOE_CHECK_ARG(bq_ptrs && bs_ptrs && offsets, "grouped_gemm_mxfp8_q: null pointer table / offsets");
+  if (M == 0) return CSMOE_OK;
+  if (Cq)
+    return gg8f_rowspace_q(Aq, lda, As, ldas, bq_ptrs, bs_ptrs, ldb, ldbs, bias_ptrs, offsets, E, M, N, Kd, C, C2, ldc, Cq, ldcq, Cs,
+                           ldcs, act, nullptr, nullptr, nullptr, (hipStream_t)stream);
+  return gg8f_rowspace(Aq, lda, As, ldas, bq_ptrs, bs_ptrs, ldb, ldbs, bias_ptrs, offsets, E, M, N, Kd, C, C2, aux, ldc, epilogue, act,
+                       nullptr, nullptr, nullptr, (hipStream_t)stream);
+}
+
+int csmoe_dense_gemm_mxfp8_q(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Bq, const void* Bs, int64_t ldb,
+                             int64_t ldbs, const void* bias, int M, int N, int Kd, void* C, void* C2, const void* aux, int64_t ldc,
+                             int epilogue, int act, void* Cq, int64_t ldcq, void* Cs, int64_t ldcs, csmoe_stream_t stream) {
+  if (int rc = fp8_q_args("dense_gemm_mxfp8_q", 1, 1, M, N, Kd, lda, ldas, ldb, ldbs, Aq, As, C, C2, aux, ldc, Cq, ldcq, Cs, ldcs,
+                          epilogue, act)) return rc;
+  if (M == 0) return CSMOE_OK;
+  CSMOE_CHECK_ARG(Bq && Bs, "dense_gemm_mxfp8_q: null pointer");
+  if ((((uintptr_t)Bq | (uintptr_t)bias) & 15) || ((uintptr_t)Bs & 3)) {
+    csmoe_set_error("dense_gemm_mxfp8_q: Bq and bias must be 16-byte aligned, Bs 4-byte");
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  if (Cq)
+    return gg8f_rowspace_q(Aq, lda, As, ldas, nullptr, nullptr, ldb, ldbs, nullptr, nullptr, 1, M, N, Kd, C, C2, ldc, Cq, ldcq, Cs, ldcs,
+                           act, Bq, Bs, bias, (hipStream_t)stream);
   return gg8f_rowspace(Aq, lda, As, ldas, nullptr, nullptr, ldb, ldbs, nullptr, nullptr, 1, M, N, Kd, C, C2, aux, ldc, epilogue, act,
                        Bq, Bs, bias, (hipStream_t)stream);
 }

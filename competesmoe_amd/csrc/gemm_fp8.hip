@@ -14,7 +14,7 @@
 //   * the e8m0 scales travel by LDS-DMA too (4 bytes per row and K-tile: one 256-byte wave-instruction per wave and K-tile --
 //     waves 0-3 the 256 row scales, waves 4-7 the 256 column scales), are read as bytes in phase A and handed to the MFMA as
 //     per-lane scale operands (lane l supplies the scale of ITS 32-element block).
-#include "gemm_epilogue.h"
+#include "gemm_epilogue_q.h"
 #include <algorithm>
 
 using namespace ggt;
@@ -41,82 +41,27 @@ struct Fp8Args {
 };
 
 __global__ void __launch_bounds__(512, 2) gg8f_kernel(Fp8Args p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-
-  const int nct = (p.NC + BN8 - 1) / BN8;
-  FIND_TILE_OR_RETURN(tp, p.offsets, p.E, p.single_M, BM8, nct, 0, 0);
-  TILE_VARS_8W(tp, BM8, BN8);
-  // the DMA helpers count the reduction in 2-byte units (they were written for bf16): 64 units = one 128-byte K-tile
-  const int red_len = p.Kd >> 1;
-  const int ncols = min(BN8, p.NC - tc0);
-
-  const unsigned ldr_b = (unsigned)p.ld_r, ldc_b = (unsigned)p.ld_c;
-  const unsigned ldrs = (unsigned)p.ld_rs, ldcs = (unsigned)p.ld_cs;
-  const unsigned nsb = (unsigned)(p.Kd >> 5);          // scale bytes per row
-  __amdgpu_buffer_rsrc_t rs_r, rs_c, rs_rs, rs_cs;
-  unsigned vb_rl[2], vb_rh[2], vb_cl[2], vb_ch[2];
-  int ax_r[2], ax_c[2], ax_dummy[2];
-  rs_r = make_rsrc(p.R + (int64_t)row0 * ldr_b, (unsigned)rows * ldr_b);
-  dma_setup<KC, 2>(vb_rl, ax_r, ldr_b, 0, 0, 7, 0, 0, wave, lane);
-  dma_setup<KC, 2>(vb_rh, ax_dummy, ldr_b, 0, 0, 7, 0, 128, wave, lane);
-  const char* wb = (const char*)(p.c_ptrs ? p.c_ptrs[e] : p.single_B);
-  const char* wsb = (const char*)(p.cs_ptrs ? p.cs_ptrs[e] : p.single_BS);
-  rs_c = make_rsrc(wb + (int64_t)tc0 * ldc_b, (unsigned)ncols * ldc_b);
-  dma_setup<KC, 2>(vb_cl, ax_c, ldc_b, 0, 0, 7, 0, 0, wave, lane);
-  dma_setup<KC, 2>(vb_ch, ax_dummy, ldc_b, 0, 0, 7, 0, 128, wave, lane);
-  rs_rs = make_rsrc(p.RS + (int64_t)row0 * ldrs, (unsigned)rows * ldrs);
-  rs_cs = make_rsrc(wsb + (int64_t)tc0 * ldcs, (unsigned)ncols * ldcs);
-  // scale piece of this wave: waves 0-3 rows (wave * 64 + lane) of the tile, waves 4-7 columns ((wave - 4) * 64 + lane)
-  const bool sc_rows = wave < 4;
-  const unsigned sc_vbase = (unsigned)((wave & 3) * 64 + lane) * (sc_rows ? ldrs : ldcs);
-
-  // ---------------- LDS read addressing ----------------
-  const int g = lane >> 4, i16 = lane & 15;
-  const int sw = (i16 >> 1) & 7;
-  const int f_lo = i16 * 128 + ((g ^ sw) << 4);                // chunk g     of this lane's row (source-side swizzle of dma_setup)
-  const int f_hi = i16 * 128 + (((g + 4) ^ sw) << 4);          // chunk g + 4
-  const int r_blk0 = wm * 4, c_blk0 = wn * 2;
-
-  ZERO_ACC(acc, 4, 8);
-
-  const int nk = (p.Kd + 127) / 128;
-
-#define SCSLOT(tile) (smem + SC_OFF + ((tile) & 1) * 2048)
-#define ISSUE_RL(tile) dma_tile<KC, 2>(rs_r, SLOT(0, tile), vb_rl, ax_r, (tile) * 64, red_len, ldr_b, wave)
-#define ISSUE_CL(tile) dma_tile<KC, 2>(rs_c, SLOT(1, tile), vb_cl, ax_c, (tile) * 64, red_len, ldc_b, wave)
-#define ISSUE_CH(tile) dma_tile<KC, 2>(rs_c, SLOT(2, tile), vb_ch, ax_c, (tile) * 64, red_len, ldc_b, wave)
-#define ISSUE_RH(tile) dma_tile<KC, 2>(rs_r, SLOT(3, tile), vb_rh, ax_r, (tile) * 64, red_len, ldr_b, wave)
-  // 4 scale bytes (the K-tile's four 32-element blocks) of one row / column per lane
-#define ISSUE_SC(tile)                                                                                              \
-  do {                                                                                                              \
-    unsigned vo_ = sc_vbase + (unsigned)(tile) * 4u;                                                                \
-    if ((unsigned)(tile) * 4u >= nsb) vo_ = OOB;                                                                    \
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(sc_rows ? rs_rs : rs_cs, (lds_void*)(SCSLOT(tile) + wave * 256), 4,    \
-                                             vo_, 0, 0, 0);                                                         \
-  } while (0)
-#define FRAG(img, blk) ({                                                              \
-    const i32x4 lo_ = *(const i32x4*)((img) + (blk) * 2048 + f_lo);                     \
-    const i32x4 hi_ = *(const i32x4*)((img) + (blk) * 2048 + f_hi);                     \
-    i32x8{lo_[0], lo_[1], lo_[2], lo_[3], hi_[0], hi_[1], hi_[2], hi_[3]}; })
-#define MFMA8(ACC, FC, FR, SC, SR) \
-  ACC = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(FC, FR, ACC, 0, 0, 0, SC, 0, SR)
-
-  const int rows_here = rows - wm * 64;
-  const int cols_here = ncols - wn * 32;
-  const bool rlo = rows_here > 0, rhi = rows_here > 128, clo = cols_here > 0, chi = cols_here > 128;
-
-#include "gemm_loop_fp8.inc"
-
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
+#include "gemm_fp8_tile.inc"
 
   // ---------------- epilogue: the bf16 kernels' (gemm_epilogue.h) ----------------
   const EpiArgs ea{p.C, p.C2, p.aux, p.bias_ptrs ? p.bias_ptrs[e] : p.single_bias, p.ldc, p.epilogue, p.act, p.NC};
   rowspace_epilogue(ea, acc, smem, row0, rows, tc0, wm, wn, lane);
+}
+
+// The same tile with the quantised activated output of gemm_epilogue_q.h (CSMOE_EPI_BIAS_ACT only): a kernel of its own, so that
+// gg8f_kernel's arguments, registers and code stay what they are for every launch without Cq / Cs.
+struct Fp8QArgs {
+  Fp8Args a;
+  uint8_t* Cq; uint8_t* Cs; int64_t ldcq, ldcs;    // [M, N] e4m3, [M, N/32] e8m0
+};
+
+__global__ void __launch_bounds__(512, 2) gg8fq_kernel(Fp8QArgs pq) {
+  const Fp8Args& p = pq.a;
+#include "gemm_fp8_tile.inc"
+
+  const EpiArgs ea{p.C, p.C2, nullptr, p.bias_ptrs ? p.bias_ptrs[e] : p.single_bias, p.ldc, CSMOE_EPI_BIAS_ACT, p.act, p.NC};
+  const EpiQArgs eq{pq.Cq, pq.Cs, pq.ldcq, pq.ldcs};
+  rowspace_epilogue_q(ea, eq, acc, smem, row0, rows, tc0, wm, wn, lane);
 }
 
 }  // namespace
@@ -136,6 +81,27 @@ int gg8f_rowspace(const void* Aq, int64_t lda, const void* As, int64_t ldas, con
   if ((rc = set_dyn_lds<gg8f_kernel, LDS8_BYTES>())) return rc;
   hipLaunchKernelGGL(gg8f_kernel, dim3(grid), dim3(512), LDS8_BYTES, st, p);
   CSMOE_CHECK_LAUNCH("grouped_gemm_mxfp8");
+  return CSMOE_OK;
+}
+
+// gg8f_rowspace with Cq [M, ldcq] / Cs [M, ldcs] next to (or instead of) C / C2: CSMOE_EPI_BIAS_ACT, N % 32 == 0 (the caller's checks)
+int gg8f_rowspace_q(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* const* bq_ptrs, const void* const* bs_ptrs,
+                    int64_t ldb, int64_t ldbs, const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd,
+                    void* C, void* C2, int64_t ldc, void* Cq, int64_t ldcq, void* Cs, int64_t ldcs, int act, const void* single_B,
+                    const void* single_BS, const void* single_bias, hipStream_t st) {
+  Fp8QArgs pq{};
+  Fp8Args& p = pq.a;
+  p.R = (const uint8_t*)Aq; p.ld_r = lda; p.RS = (const uint8_t*)As; p.ld_rs = ldas;
+  p.c_ptrs = bq_ptrs; p.cs_ptrs = bs_ptrs; p.ld_c = ldb; p.ld_cs = ldbs; p.single_B = single_B; p.single_BS = single_BS;
+  p.bias_ptrs = bias_ptrs; p.single_bias = single_bias; p.offsets = offsets; p.E = E; p.single_M = M;
+  p.NC = N; p.Kd = Kd; p.C = C; p.C2 = C2; p.aux = nullptr; p.ldc = ldc; p.epilogue = CSMOE_EPI_BIAS_ACT; p.act = act;
+  pq.Cq = (uint8_t*)Cq; pq.Cs = (uint8_t*)Cs; pq.ldcq = ldcq; pq.ldcs = ldcs;
+  unsigned grid;
+  int rc = grid_1d("grouped_gemm_mxfp8_q", rowspace_tiles(M, E, N, BM8, BN8), &grid);
+  if (rc || !grid) return rc;
+  if ((rc = set_dyn_lds<gg8fq_kernel, LDS8_BYTES>())) return rc;
+  hipLaunchKernelGGL(gg8fq_kernel, dim3(grid), dim3(512), LDS8_BYTES, st, pq);
+  CSMOE_CHECK_LAUNCH("grouped_gemm_mxfp8_q");
   return CSMOE_OK;
 }
 

@@ -1494,6 +1494,12 @@ class MoEFFNPackedFP8(_ForwardAware):
                 y = _ffn_fp8_decode(x2, keys, values, bias, act, bins.offsets, bins.perm, bins.K)
             ctx.saved = None                     # no backward can follow
             return ops.combine(y, bins, idx, w, combine_mode, T)
+        return MoEFFNPackedFP8._forward(ctx, x2, w, idx, bins, keys, values, bias, act, combine_mode, cache, wgrad_fp8)
+
+    @staticmethod
+    def _forward(ctx, x2, w, idx, bins, keys, values, bias, act: int, combine_mode: int, cache: bool, wgrad_fp8: bool):
+        """The tiled (training) form on checked inputs -- shared with MoEFFNPackedFP8Slots, which takes its slot rows from ctx.saved."""
+        T = x2.shape[0]
         xs, xq, xsc = ops.dispatch_tokens_mxfp8(x2, bins)       # the gather and the quantiser in one pass (CSMOE_DISPATCH_QUANT=0: two)
         (kq_b, ks_b), (kq, ks) = _quantize_weight_both(keys, cache)        # backward pair [E, D, F]; forward pair [E, F, D] (reduction over D)
         b_op, b1 = _fp8_bias_table(bias)
@@ -1513,13 +1519,21 @@ class MoEFFNPackedFP8(_ForwardAware):
 
     @staticmethod
     def backward(ctx, dout):
-        bins, xs, hpre, hact, y, _ = _take_saved(ctx)
+        dx2, dw, gk, gv, gb = MoEFFNPackedFP8._backward(ctx, _take_saved(ctx), dout)
+        return dx2, dw, None, gk, gv, gb, None, None, None, None, None
+
+    @staticmethod
+    def _backward(ctx, saved, dout, dy_extra=None):
+        """(dx2, dw, gk, gv, gb) -- shared with MoEFFNPackedFP8Slots, whose per-slot output gradient arrives as `dy_extra` (binned order)."""
+        bins, xs, hpre, hact, y, _ = saved
         act, bias_dtype = ctx.cfg
         keys, values = ctx.keys, ctx.values
         E, D, F = keys.shape
         T = dout.shape[0]
         need_dw = ctx.needs_input_grad[1]
         dy, dw = ops.combine_bwd(dout.contiguous(), y if need_dw else None, bins, ctx.w, want_dw=need_dw, act_dtype=torch.bfloat16)
+        if dy_extra is not None:
+            dy = dy + dy_extra
         kq, ks, vq, vs = ctx.wq
         ctx.wq = None
         f8w = ctx.wgrad_fp8
@@ -1559,7 +1573,103 @@ class MoEFFNPackedFP8(_ForwardAware):
                 dhq, dhs = ops.quantize_mxfp8(dh)
             dxs = ops.grouped_gemm_mxfp8(dhq, dhs, kq, ks, bins.offsets)   # keys as stored: dxs = dh @ keys[e]^T
             dx2 = ops.dispatch_rows_bwd(dxs, bins, T)
-        return dx2, dw, None, gk, gv, gb, None, None, None, None, None
+        return dx2, dw, gk, gv, gb
+
+
+class MoEFFNPackedFP8Slots(_ForwardAware):
+    """MoEFFNPackedFP8 that also returns the expert outputs per (token, k) slot, [T, K, Dout] -- MoEFFNPackedSlots for fp8 experts: the
+    `topk` outputs of a competition step for the diversity loss come from the sparse step's own rows, so that the dense pass
+    (CompetitionAffinityPackedFP8) keeps none.  Same launches as MoEFFNPackedFP8 plus the gather of the slot rows; the backward adds
+    their gradient to dy after the combine's backward."""
+
+    @staticmethod
+    def forward(ctx, x2, w, idx, keys, values, bias, act: int, combine_mode: int, cache: bool = False, wgrad_fp8: bool = False):
+        # always the tiled form: the decode path of MoEFFNPackedFP8 keeps no y to take the slot rows from
+        x2, w = _fp8_rows_and_weights(x2, w)
+        bins = ops.bin_tokens(idx, keys.shape[0])
+        out = MoEFFNPackedFP8._forward(ctx, x2, w, idx, bins, keys, values, bias, act, combine_mode, cache, wgrad_fp8)
+        y = ctx.saved[4]
+        y_tk = ops.dispatch_rows(y, _SlotMap(bins.slot_of, bins.n))
+        return out, y_tk.view(x2.shape[0], idx.shape[-1], y.shape[-1])
+
+    @staticmethod
+    def backward(ctx, dout, dy_tk):
+        saved = _take_saved(ctx)
+        bins = saved[0]
+        extra = None
+        if dy_tk is not None:
+            extra = ops.dispatch_rows(dy_tk.reshape(bins.n, -1).contiguous(), _SlotMap(bins.perm, bins.n))
+        if dout is None:
+            dout = torch.zeros(ctx.w.shape[0], ctx.values.shape[2], dtype=saved[4].dtype, device=ctx.w.device)
+        dx2, dw, gk, gv, gb = MoEFFNPackedFP8._backward(ctx, saved, dout, extra)
+        return dx2, dw, None, gk, gv, gb, None, None, None, None
+
+
+class CompetitionAffinityPackedFP8(torch.autograd.Function):
+    """CompetitionAffinityPacked on the MXFP8 pipe (`args.fp8_competition`): aff[t, e] = mean_d softplus(expert_e(x[t]))[d] for every
+    expert, from the SAME quantised tables the sparse step multiplies (_quantize_weight_both: with `cache` the entries it reuses).
+    x is quantised once for all experts; per expert GEMM 1 writes only the MXFP8 form of its activated output (csmoe_dense_gemm_mxfp8_q:
+    no bf16 hact, no quantiser launch) and GEMM 2 reduces softplus(y) in its epilogue.  The backward recomputes both per expert (GEMM 1
+    then also writes hpre / hact), forms dy in GEMM 2's epilogue, and runs dH and dX on the quantised dy / dh with the backward tables.
+    Six of the eight GEMM passes per expert are MXFP8; the two weight-gradient products stay bf16 (`args.fp8_wgrad` does not apply
+    to this pass: its token-dim quantiser works on binned rows).  dx is summed over the experts by `add_` (the fp8 kernel has no
+    accumulating epilogue).  Saves x and the parameters only; the quantised tables are held until the backward like
+    MoEFFNPackedFP8's.  No counterpart upstream (the reference has no fp8)."""
+
+    @staticmethod
+    def forward(ctx, x2, keys, values, act: int, fp32_affinity: bool, cache: bool = False):
+        x2 = x2.contiguous()
+        if x2.dtype != torch.bfloat16:
+            raise ValueError("competesmoe_amd: the fp8 competition pass takes bf16 activations (run under bf16 autocast)")
+        E = keys.shape[0]
+        aff = torch.empty(x2.shape[0], E, dtype=torch.float32 if fp32_affinity else x2.dtype, device=x2.device)
+        xq, xsc = ops.quantize_mxfp8(x2)
+        (kq_b, ks_b), (kq, ks) = _quantize_weight_both(keys, cache)        # backward pair [E, D, F]; forward pair [E, F, D]
+        (vq_b, vs_b), (vq, vs) = _quantize_weight_both(values, cache)      # backward pair [E, F, Dout]; forward pair [E, Dout, F]
+        for e in range(E):
+            _, _, hq, hs = ops.dense_gemm_mxfp8_q(xq, xsc, kq[e], ks[e], act=act)
+            ops.dense_gemm_affinity_mxfp8(hq, hs, vq[e], vs[e], None, aff[:, e], rounded=not fp32_affinity)
+            del hq, hs
+        ctx.save_for_backward(x2, keys, values)
+        ctx.wq = (kq, ks, vq, vs, kq_b, ks_b, vq_b, vs_b)
+        ctx.cfg = (act, fp32_affinity)
+        return aff
+
+    @staticmethod
+    def backward(ctx, daff):
+        x2, keys, values = ctx.saved_tensors
+        act, fp32_affinity = ctx.cfg
+        if ctx.wq is None:
+            raise RuntimeError("competesmoe_amd: the fp8 competition pass releases its quantised tables in the first backward pass; "
+                               "a second backward through the same graph is not supported -- run the forward again")
+        kq, ks, vq, vs, kq_b, ks_b, vq_b, vs_b = ctx.wq
+        ctx.wq = None
+        E = keys.shape[0]
+        daff = daff.contiguous()
+        gk = torch.empty_like(keys) if ctx.needs_input_grad[1] else None
+        gv = torch.empty_like(values) if ctx.needs_input_grad[2] else None
+        dx = None
+        xq, xsc = ops.quantize_mxfp8(x2)
+        for e in range(E):
+            hpre, hact, hq, hs = ops.dense_gemm_mxfp8_q(xq, xsc, kq[e], ks[e], act=act, want_c=act != L.ACT_RELU, want_c2=True)
+            dy = ops.dense_gemm_affinity_grad_mxfp8(hq, hs, vq[e], vs[e], None, daff[:, e].float().contiguous(),
+                                                    rounded=not fp32_affinity)
+            del hq, hs
+            dyq, dys = ops.quantize_mxfp8(dy)
+            dh = ops.dense_gemm_mxfp8(dyq, dys, vq_b[e], vs_b[e], epilogue=L.EPI_ACTGRAD, act=act,          # values[e] as stored
+                                      aux=hpre if hpre is not None else hact)
+            del dyq, dys
+            if gv is not None:
+                gv[e] = _dense_wgrad(hact, dy, values.dtype)
+            if gk is not None:
+                gk[e] = _dense_wgrad(x2, dh, keys.dtype)
+            if ctx.needs_input_grad[0]:
+                dhq, dhs = ops.quantize_mxfp8(dh)
+                dxe = ops.dense_gemm_mxfp8(dhq, dhs, kq_b[e], ks_b[e])     # keys[e] as stored: dx_e = dh @ keys[e]^T
+                dx = dxe if dx is None else dx.add_(dxe)
+                del dhq, dhs
+            del hpre, hact, dy, dh
+        return dx, gk, gv, None, None, None
 
 
 class DenseFFNFP8(_ForwardAware):

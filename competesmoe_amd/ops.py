@@ -1175,6 +1175,92 @@ def dense_gemm_mxfp8(Aq: torch.Tensor, As: torch.Tensor, Bq: torch.Tensor, Bs: t
     return (Cm, C2) if want_c2 else Cm
 
 
+# ---- the tiled MXFP8 GEMM with a quantised activated output, and the affinity epilogues on MXFP8 operands (csrc/gemm_epilogue_q.h)
+def gemm_mxfp8_q_ok(M: int, N: int, Kd: int, epilogue: int = L.EPI_BIAS_ACT, quant_out: bool = True, dense: bool = True) -> bool:
+    """Does csmoe_dense_gemm_mxfp8_q / csmoe_grouped_gemm_mxfp8_q take this launch with contiguous operands (Kd % 128, N % 8 -- % 32
+    with the quantised output; `dense` admits the affinity epilogues)?  A host query."""
+    ldc = (N + 255) // 256 if epilogue == L.EPI_SOFTPLUS_ROWSUM else N
+    return bool(lib.csmoe_gemm_mxfp8_q_ok(M, N, Kd, Kd, Kd // 32, Kd, Kd // 32, ldc, N, N // 32, epilogue, int(quant_out), int(dense)))
+
+
+def _q_outputs(M: int, N: int, dev, want_c: bool, want_c2: bool, out_q, out_s):
+    """(C, C2, Cq, Cs) of a quantised-output launch; `out_q` [M, N] / `out_s` [M, N/32] (uint8, unit column stride): views to write into."""
+    Cm = torch.empty(M, N, dtype=torch.bfloat16, device=dev) if want_c else None
+    C2 = torch.empty(M, N, dtype=torch.bfloat16, device=dev) if want_c2 else None
+    if (out_q is None) != (out_s is None):
+        raise ValueError("csmoe gemm_mxfp8_q: `out_q` and `out_s` go together")
+    if out_q is None:
+        out_q = torch.empty(M, N, dtype=torch.uint8, device=dev)
+        out_s = torch.empty(M, N // 32, dtype=torch.uint8, device=dev)
+    elif (out_q.shape != (M, N) or out_s.shape != (M, N // 32) or out_q.dtype != torch.uint8 or out_s.dtype != torch.uint8
+          or out_q.stride(1) != 1 or out_s.stride(1) != 1):
+        raise ValueError("csmoe gemm_mxfp8_q: `out_q` [M, N] / `out_s` [M, N/32] must be uint8 with unit column stride")
+    return Cm, C2, out_q, out_s
+
+
+def grouped_gemm_mxfp8_q(Aq: torch.Tensor, As: torch.Tensor, Bq: torch.Tensor, Bs: torch.Tensor, offsets: torch.Tensor,
+                         bias_ptrs: Optional[torch.Tensor] = None, act: int = L.ACT_NONE, want_c: bool = False, want_c2: bool = False,
+                         out_q: Optional[torch.Tensor] = None, out_s: Optional[torch.Tensor] = None):
+    """grouped_gemm_mxfp8 with EPI_BIAS_ACT whose activated output is ALSO (or only) written as MXFP8 (csmoe_grouped_gemm_mxfp8_q):
+    returns (C or None, C2 or None, Cq [M, N], Cs [M, N/32]); Cq / Cs are the bytes quantize_mxfp8(C2) would give.  N % 32 == 0."""
+    M, Kd = Aq.shape
+    E, N, _ = Bq.shape
+    Cm, C2, Cq, Cs = _q_outputs(M, N, Aq.device, want_c, want_c2, out_q, out_s)
+    bq = ptr_table(Bq, E, N * Kd)
+    bs = ptr_table(Bs, E, N * (Kd // 32))
+    with _timed("grouped_gemm_mxfp8_q", 2.0 * M * N * Kd):
+        L.check(lib.csmoe_grouped_gemm_mxfp8_q(Aq.data_ptr(), Kd, As.data_ptr(), Kd // 32, bq.data_ptr(), bs.data_ptr(), Kd, Kd // 32,
+                                               _ptr(bias_ptrs), offsets.data_ptr(), E, M, N, Kd, _ptr(Cm), _ptr(C2), None, N,
+                                               L.EPI_BIAS_ACT, act, Cq.data_ptr(), Cq.stride(0), Cs.data_ptr(), Cs.stride(0),
+                                               _stream()), "grouped_gemm_mxfp8_q")
+    return Cm, C2, Cq, Cs
+
+
+def dense_gemm_mxfp8_q(Aq: torch.Tensor, As: torch.Tensor, Bq: torch.Tensor, Bs: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                       act: int = L.ACT_NONE, want_c: bool = False, want_c2: bool = False, out_q: Optional[torch.Tensor] = None,
+                       out_s: Optional[torch.Tensor] = None):
+    """Dense form of grouped_gemm_mxfp8_q (csmoe_dense_gemm_mxfp8_q): Bq [N, Kd], Bs [N, Kd/32]."""
+    M, Kd = Aq.shape
+    N = Bq.shape[0]
+    Cm, C2, Cq, Cs = _q_outputs(M, N, Aq.device, want_c, want_c2, out_q, out_s)
+    with _timed("dense_gemm_mxfp8_q", 2.0 * M * N * Kd):
+        L.check(lib.csmoe_dense_gemm_mxfp8_q(Aq.data_ptr(), Kd, As.data_ptr(), Kd // 32, Bq.data_ptr(), Bs.data_ptr(), Kd, Kd // 32,
+                                             _ptr(bias), M, N, Kd, _ptr(Cm), _ptr(C2), None, N, L.EPI_BIAS_ACT, act, Cq.data_ptr(),
+                                             Cq.stride(0), Cs.data_ptr(), Cs.stride(0), _stream()), "dense_gemm_mxfp8_q")
+    return Cm, C2, Cq, Cs
+
+
+def dense_gemm_affinity_mxfp8(hq: torch.Tensor, hs: torch.Tensor, w2q: torch.Tensor, w2s: torch.Tensor, bias: Optional[torch.Tensor],
+                              aff_col: torch.Tensor, rounded: bool) -> None:
+    """dense_gemm_affinity on MXFP8 operands: aff_col[t] = mean_n softplus(round(dq(h)[t] @ dq(w2)^T (+ bias))[n]) without storing the
+    product -- csmoe_dense_gemm_mxfp8_q with the SOFTPLUS_ROWSUM epilogue + csmoe_affinity_finish.  hq [M, Kd] / hs [M, Kd/32],
+    w2q [N, Kd] / w2s [N, Kd/32]."""
+    M, Kd = hq.shape
+    N = w2q.shape[0]
+    nt = (N + 255) // 256
+    part = torch.empty(M, nt, dtype=torch.float32, device=hq.device)
+    with _timed("dense_gemm_affinity_mxfp8", 2.0 * M * N * Kd):
+        L.check(lib.csmoe_dense_gemm_mxfp8_q(hq.data_ptr(), Kd, hs.data_ptr(), Kd // 32, w2q.data_ptr(), w2s.data_ptr(), Kd, Kd // 32,
+                                             _ptr(bias), M, N, Kd, part.data_ptr(), None, None, nt, L.EPI_SOFTPLUS_ROWSUM,
+                                             _softplus_flags(rounded), None, 0, None, 0, _stream()), "dense_gemm_mxfp8_q(SOFTPLUS_ROWSUM)")
+    L.check(lib.csmoe_affinity_finish(part.data_ptr(), M, nt, N, aff_col.data_ptr(), aff_col.stride(0), _dt(aff_col), _stream()),
+            "affinity_finish")
+
+
+def dense_gemm_affinity_grad_mxfp8(hq: torch.Tensor, hs: torch.Tensor, w2q: torch.Tensor, w2s: torch.Tensor,
+                                   bias: Optional[torch.Tensor], daff: torch.Tensor, rounded: bool) -> torch.Tensor:
+    """dense_gemm_affinity_grad on MXFP8 operands: dy[t, n] = round(g[t] * sigmoid(round(dq(h)[t] @ dq(w2)^T (+ bias))[n])), g = daff / N
+    (rounded to bf16 first when `rounded`); daff fp32 [M] contiguous; dy bf16 [M, N]."""
+    M, Kd = hq.shape
+    N = w2q.shape[0]
+    dy = torch.empty(M, N, dtype=torch.bfloat16, device=hq.device)
+    with _timed("dense_gemm_affinity_grad_mxfp8", 2.0 * M * N * Kd):
+        L.check(lib.csmoe_dense_gemm_mxfp8_q(hq.data_ptr(), Kd, hs.data_ptr(), Kd // 32, w2q.data_ptr(), w2s.data_ptr(), Kd, Kd // 32,
+                                             _ptr(bias), M, N, Kd, dy.data_ptr(), None, daff.data_ptr(), N, L.EPI_SOFTPLUS_GRAD,
+                                             _softplus_flags(rounded), None, 0, None, 0, _stream()), "dense_gemm_mxfp8_q(SOFTPLUS_GRAD)")
+    return dy
+
+
 # ------------------------------------------------------------------------------------------------ MXFP8 weight gradients
 def token_pad_bound(n: int, E: int) -> int:
     """Padded token length that holds every expert's rows rounded up to 128 (csmoe_token_pad_bound): known without the counts."""

@@ -6,7 +6,8 @@ import torch.nn.functional as F
 
 from .. import _lib as L
 from .. import ops
-from ..functional import CompetitionAffinityPacked, DenseFFN, DiversityLoss, RouterSelect, SoftplusMean
+from ..functional import (CompetitionAffinityPacked, CompetitionAffinityPackedFP8, DenseFFN, DiversityLoss, RouterSelect,
+                          SoftplusMean)
 from .moe import MoE, op_dtype
 from ..schedule import draw_balanced_flips
 from .register import register_moe
@@ -28,6 +29,29 @@ class CompeteSMoE(MoE):
         self.max_compete_in_iter = args.max_compete_in_iter
         self.nb_diver = 0
         self._flips_host = {}
+        # the competition step in the lean form on the MXFP8 pipe, from the tables the sparse step multiplies
+        # (functional.CompetitionAffinityPackedFP8 + MoEFFNPackedFP8Slots); off by default, needs args.fp8_experts
+        self.fp8_competition = bool(getattr(args, "fp8_competition", False))
+        if self.fp8_competition and self._fp8_competition_ok:
+            self._check_fp8_competition()
+
+    _fp8_competition_ok = True        # False on competesmoe_ep, which refuses the flag after its own checks
+
+    def _check_fp8_competition(self):
+        if not self.fp8_experts:
+            raise ValueError("competesmoe_amd: args.fp8_competition runs the competition step on the MXFP8 tables of the experts: "
+                             "it needs args.fp8_experts")
+        _, D, Fd = self.keys.shape
+        Dout = self.values.shape[2]
+        if D % 128 or Fd % 128:
+            raise ValueError(f"competesmoe_amd: args.fp8_competition needs dmodel and expert_size to be multiples of 128, the "
+                             f"K-tile of the MXFP8 GEMM (they are the reduction dims of its two forward products); got {D} and {Fd}")
+        if Dout % 8:
+            raise ValueError(f"competesmoe_amd: args.fp8_competition needs the expert output width to be a multiple of 8 "
+                             f"(16-byte bf16 rows); got {Dout}")
+        if Dout % 128:
+            raise ValueError(f"competesmoe_amd: args.fp8_competition needs the expert output width to be a multiple of 128: the dH "
+                             f"product of the backward reduces over it on the MXFP8 GEMM; got {Dout}")
 
     # ------------------------------------------------------------------ schedule (:123-273)
     def set_total_steps(self, id_layer=0):
@@ -103,6 +127,15 @@ class CompeteSMoE(MoE):
         B, N, D = x.shape
         op = op_dtype(x)
         x2 = self.operand(x)
+        if self.fp8_competition:
+            # the lean form on MXFP8 operands: the affinities come from the quantised tables the sparse step then multiplies, the
+            # selected experts' outputs from that step (forward below: ffn_slots on fp8 experts)
+            if op != torch.bfloat16:
+                raise ValueError("competesmoe_amd: args.fp8_experts needs bf16 activations (bf16 autocast or a bf16 layer)")
+            fp32_aff = torch.is_autocast_enabled("cuda")
+            aff = CompetitionAffinityPackedFP8.apply(x2, self.keys, self.values, self.act_code, fp32_aff, self.fp8_weight_cache)
+            asm, idx, w = RouterSelect.apply(aff, self.num_selected, L.SEL_RAW, False)
+            return w.view(B, N, -1), idx.view(B, N, -1), asm.view(B, N, -1), aff.view(B, N, -1), None
         if self._lean_competition(x2):
             # without the [T, E, D] outputs: affinities from the second GEMM's epilogue, backward by recomputation, the selected
             # experts' outputs from the sparse step (forward below); functional.CompetitionAffinityPacked
@@ -125,7 +158,8 @@ class CompeteSMoE(MoE):
     def _lean_competition(self, x2) -> bool:
         """The dense pass without its stored outputs / activations?  CSMOE_COMPETITION_LEAN=1 / 0 forces it; default: when the
         stored form would keep more than 24 GiB alive (T * E * (2F + Dout) activations).  Needs the plain sparse step for the
-        selected outputs (no fp8 experts, no residual handed in by the block)."""
+        selected outputs (no fp8 experts, no residual handed in by the block).  Layers with args.fp8_competition never ask: their
+        competition step is always the lean form on the fp8 pipe."""
         import os
         E, D, Fd = self.keys.shape
         Dout = self.values.shape[2]

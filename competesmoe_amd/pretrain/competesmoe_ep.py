@@ -36,9 +36,13 @@ from .smoe_ep import EPPackedExperts, _broadcast
 @register_moe("competesmoe_ep")
 class EPCompeteSMoE(EPPackedExperts, CompeteSMoE):
     _ep_name = "competesmoe_ep"
+    _fp8_competition_ok = False
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
+        if self.fp8_competition:
+            raise ValueError("competesmoe_ep: args.fp8_competition is a single-GPU path (it needs args.fp8_experts, which this layer "
+                             "refuses)")
         rank = dist.get_rank(self.group)
         with torch.no_grad():
             _broadcast(self.w_gate.data, self.group)

@@ -19,8 +19,8 @@ import torch.nn.functional as F
 
 from .. import _lib as L
 from .. import ops
-from ..functional import (DenseFFN, DenseFFNFP8, GateLogits, GateSelect, MoEFFNPacked, MoEFFNPackedFP8, MoEFFNPackedSlots, OperandFork,
-                          RouterSelect)
+from ..functional import (DenseFFN, DenseFFNFP8, GateLogits, GateSelect, MoEFFNPacked, MoEFFNPackedFP8, MoEFFNPackedFP8Slots,
+                          MoEFFNPackedSlots, OperandFork, RouterSelect)
 from .framework_layers import LoggingLayer, OncePerIterLayer, RegularizedLayer
 
 # default of args.fp8_wgrad, read once per process (CSMOE_FP8_WGRAD=1: the expert weight gradients on the fp8 pipe too)
@@ -269,6 +269,17 @@ class MoE(LoggingLayer, RegularizedLayer, OncePerIterLayer, nn.Module):
         x2 = self.operand(x)
         K = selected_experts.shape[-1]
         wk = weights.reshape(-1, K)
+        if self.fp8_experts:
+            # the fp8 sparse step of ffn() plus its slot rows (MoEFFNPackedFP8Slots); the block's residual is added as ffn() adds it
+            if op_dtype(x) != torch.bfloat16:
+                raise ValueError("competesmoe_amd: args.fp8_experts needs bf16 activations (bf16 autocast or a bf16 layer)")
+            res, self._residual = self._residual, None
+            out, y_tk = MoEFFNPackedFP8Slots.apply(x2, wk.float().contiguous(), selected_experts.reshape(-1, K).int().contiguous(),
+                                                   self.keys, self.values, self.bias, self.act_code, L.COMBINE_DOT,
+                                                   self.fp8_weight_cache, self.fp8_wgrad)
+            if res is not None:
+                out = res + out.view(res.shape)
+            return out.view(*shp[:-1], -1), y_tk.view(*shp[:-1], K, -1)
         out, y_tk = MoEFFNPackedSlots.apply(x2, wk.float().contiguous(), selected_experts.reshape(-1, K).int().contiguous(),
                                             self.keys, self.values, self.bias, None, self.act_code, L.COMBINE_DOT)
         return out.view(*shp[:-1], -1), y_tk.view(*shp[:-1], K, -1)

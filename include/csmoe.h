@@ -473,6 +473,31 @@ int csmoe_grouped_gemm_mxfp8(const void* Aq, int64_t lda, const void* As, int64_
 int csmoe_dense_gemm_mxfp8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Bq, const void* Bs, int64_t ldb,
                            int64_t ldbs, const void* bias, int M, int N, int Kd, void* C, void* C2, const void* aux, int64_t ldc,
                            int epilogue, int act, csmoe_stream_t stream);
+/* The two entries above with a quantised activated output, and on the dense entry the affinity epilogues of the competition pass
+ * (the entries above keep their signatures and their refusals).  Same operands, shape rule and rounding points; in addition:
+ *   - Cq [M, N] e4m3 (ldcq) and Cs [M, N/32] e8m0 (ldcs), both null or both given, CSMOE_EPI_BIAS_ACT only: the MX quantisation of
+ *     the bf16-ROUNDED activated output, blocks along N -- the operand orientation of the GEMM that reads the activations next.
+ *     Contract: Cq and Cs are, byte for byte, what csmoe_quantize_mxfp8 (transpose = 0) writes for the bf16 C2 of the same launch,
+ *     all-zero blocks (scale byte 0), NaN and Inf included; C and C2, when given, are the bytes the entries above write.  C, C2 and
+ *     Cq are each optional (one of them must be given).  Needs N % 32 == 0 (no block straddles the matrix edge), Cq 16-byte aligned
+ *     and ldcq % 16 == 0, else CSMOE_ERR_UNSUPPORTED.  Without Cq the call launches what the entries above launch.
+ *   - csmoe_dense_gemm_mxfp8_q also takes CSMOE_EPI_SOFTPLUS_ROWSUM (C = the FP32 table [M, ceil(N/256)], ldc its row stride; closed
+ *     by csmoe_affinity_finish) and CSMOE_EPI_SOFTPLUS_GRAD (aux = FP32 d aff [M], required), with `act` = their flag bits, as
+ *     csmoe_dense_gemm does on bf16 operands.
+ * Returns CSMOE_ERR_INVALID for an argument combination that makes no sense (Cq without Cs, Cq with another epilogue, SOFTPLUS_GRAD
+ * without aux, a leading dimension too small, null operands) and CSMOE_ERR_UNSUPPORTED for CSMOE_EPI_ACCUM or a shape / alignment
+ * the rule rejects, with a message, before any pointer is read and before anything is launched; M == 0 is CSMOE_OK.
+ * csmoe_gemm_mxfp8_q_ok: the shape rule as a pure host query (0 / 1; ldcq / ldcs are looked at only with quant_out; `dense`
+ * admits the affinity epilogues).  No counterpart upstream (the reference has no fp8). */
+int csmoe_grouped_gemm_mxfp8_q(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* const* bq_ptrs,
+                               const void* const* bs_ptrs, int64_t ldb, int64_t ldbs, const void* const* bias_ptrs,
+                               const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2, const void* aux, int64_t ldc,
+                               int epilogue, int act, void* Cq, int64_t ldcq, void* Cs, int64_t ldcs, csmoe_stream_t stream);
+int csmoe_dense_gemm_mxfp8_q(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Bq, const void* Bs, int64_t ldb,
+                             int64_t ldbs, const void* bias, int M, int N, int Kd, void* C, void* C2, const void* aux, int64_t ldc,
+                             int epilogue, int act, void* Cq, int64_t ldcq, void* Cs, int64_t ldcs, csmoe_stream_t stream);
+int csmoe_gemm_mxfp8_q_ok(int M, int N, int Kd, int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc, int64_t ldcq,
+                          int64_t ldcs, int epilogue, int quant_out, int dense);
 /* Few-row (decode) form of csmoe_grouped_gemm_mxfp8 (csrc/gemm_skinny_fp8.hip): the weight streamer of csmoe_grouped_gemm_skinny
  * on MXFP8 operands, one v_mfma_scale_f32_16x16x128_f8f6f4 per 128-element K-step, the weights (half the bytes of bf16) read once
  * per 16-row block straight into registers.  For every expert e and binned row m in [offsets[e], offsets[e+1])
