@@ -50,6 +50,9 @@ SIGNATURES = {
     "csmoe_gate_select_ok": (_i, [_i, _i, _i, _i, _i]),
     "csmoe_gate_select_rows": (_i, []),
     "csmoe_gate_select": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, C.c_float, _i, _p, _p, _p, _p, _p, _p]),
+    "csmoe_decode_route_ok": (_i, [_i, _i, _i, _i, _i, _i]),
+    "csmoe_decode_route_workspace_bytes": (_l, [_i]),
+    "csmoe_decode_route": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, C.c_float, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "csmoe_cosine_select_ok": (_i, [_i, _i, _i, _i, _i]),
     "csmoe_cosine_select_work_ints": (_l, [_i]),
     "csmoe_cosine_select": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, C.c_float, C.c_float, _i, _p, _p, _p, _p, _p, _p, _p, _p]),

@@ -84,6 +84,11 @@ int k_bin_tokens_hist(const int32_t*, int, int, int, const int32_t*, int32_t*, i
 bool k_gate_select_ok(int T, int D, int E, int K, int dtype, const void* x, const void* wg);
 int k_gate_select_rows();
 int k_gate_select(const void*, const void*, int, int, int, int, int, int, float, void*, float*, int32_t*, float*, int32_t*, hipStream_t);
+bool k_decode_route_ok(int T, int D, int E, int K, int dtype, int want_quant);
+int64_t k_decode_route_workspace_bytes(int T);
+int k_decode_route(const void* x, const void* wg, int T, int D, int E, int K, int mode, int round_sum_bf16, float sel_param, void* logits,
+                   float* softmax, int32_t* idx, float* w, int32_t* counts, int32_t* offsets, int32_t* perm, int32_t* slot_of, void* xq,
+                   void* xs, void* workspace, hipStream_t st);
 bool k_cosine_select_ok(int T, int D, int E, int K, int dtype, const void* x, const void* wr);
 int64_t k_cosine_select_work_ints(int T);
 int k_cosine_select(const void* x, const void* wr, const float* emb, int T, int D, int E, int K, int flags, float temperature, float eps,
@@ -324,6 +329,36 @@ int csmoe_gate_select(const void* x, const void* w_gate, int T, int D, int E, in
   CSMOE_CHECK_ARG(x && w_gate && logits && idx && w, "gate_select: null pointer");
   return k_gate_select(x, w_gate, T, D, E, K, sel_mode, round_sum_bf16, sel_param, logits, softmax, idx, w, block_hist,
                        (hipStream_t)stream);
+}
+
+// ---- decode front end: decode_route.hip.  Bad arguments (CSMOE_ERR_INVALID) and shapes the rule rejects (CSMOE_ERR_UNSUPPORTED) are
+// decided before any pointer is read and before anything is launched; T == 0 is CSMOE_OK.
+int csmoe_decode_route_ok(int T, int D, int E, int K, int dtype, int want_quant) {
+  return k_decode_route_ok(T, D, E, K, dtype, want_quant) ? 1 : 0;
+}
+
+int64_t csmoe_decode_route_workspace_bytes(int T) { return k_decode_route_workspace_bytes(T); }
+
+int csmoe_decode_route(const void* x, const void* w_gate, int T, int D, int E, int K, int sel_mode, int round_sum_bf16, float sel_param,
+                       int dtype, void* logits, float* softmax, int32_t* idx, float* w, int32_t* counts, int32_t* offsets,
+                       int32_t* perm, int32_t* slot_of, void* xq, void* xs, void* workspace, csmoe_stream_t stream) {
+  CSMOE_CHECK_ARG(dtype_ok(dtype), "decode_route: bad dtype %d", dtype);
+  CSMOE_CHECK_ARG(T >= 0 && D > 0 && E > 0, "decode_route: bad shape T=%d D=%d E=%d", T, D, E);
+  CSMOE_CHECK_ARG(K > 0 && K <= E && K <= 64, "decode_route: K=%d out of range (1..min(E,64)), E=%d", K, E);
+  CSMOE_CHECK_ARG(sel_mode >= 0 && sel_mode <= 6, "decode_route: bad mode %d", sel_mode);
+  CSMOE_CHECK_ARG(sel_mode != CSMOE_SEL_TOPK_SIGMOID || sel_param != 0.f, "decode_route: SEL_TOPK_SIGMOID needs a non-zero scale");
+  CSMOE_CHECK_ARG(sel_mode != CSMOE_SEL_TEMP_SOFTMAX_TOPK || sel_param > 0.f,
+                  "decode_route: SEL_TEMP_SOFTMAX_TOPK needs a positive temperature");
+  CSMOE_CHECK_ARG((xq == nullptr) == (xs == nullptr), "decode_route: xq and xs come together");
+  if (T == 0) return CSMOE_OK;
+  if (!k_decode_route_ok(T, D, E, K, dtype, xq != nullptr) || ((((uintptr_t)x | (uintptr_t)w_gate | (uintptr_t)xq) & 15) != 0)) {
+    csmoe_set_error("decode_route: needs bf16, T * K <= 1024, E <= 256, D a multiple of 8 (of 32 with a quantised output) and 16-byte "
+                    "aligned operands (csmoe_decode_route_ok); T=%d D=%d E=%d K=%d", T, D, E, K);
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  CSMOE_CHECK_ARG(x && w_gate && logits && idx && w && counts && offsets && perm && slot_of && workspace, "decode_route: null pointer");
+  return k_decode_route(x, w_gate, T, D, E, K, sel_mode, round_sum_bf16, sel_param, logits, softmax, idx, w, counts, offsets, perm,
+                        slot_of, xq, xs, workspace, (hipStream_t)stream);
 }
 
 // 16-B vector path needs 16-B aligned rows; otherwise the kernel copies 2 bytes at a time

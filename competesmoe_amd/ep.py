@@ -895,6 +895,7 @@ class EPSMoeLayer(MoeLayer):
     """`smoe` with expert-parallel experts.  `num_of_experts` is the GLOBAL expert count; `expert` is an nn.ModuleList
     with this rank's E/P local experts (global ids rank*E/P ...).  The gate is replicated: its gradient is summed over the
     group after backward (tokens are data-parallel); expert gradients are local by construction."""
+    _decode_front_ok = False          # routing stays on the launches the exchange was built around
 
     def __init__(self, in_embed_dim=768, out_embed_dim=768, num_of_experts=4, num_selected=2, expert=None, args=None, group=None,
                  chunks: Optional[int] = None, direct: Optional[bool] = None):
@@ -1005,6 +1006,7 @@ class EPCompeteSMoE(MoeLayer):
     the K winners (through the exchange) follow the single-GPU code.  The diversity loss takes the winners' outputs from the
     sparse pass (they live on other ranks; same values as the dense outputs the single-GPU layer gathers from).
     The reference has no expert parallelism: the contract is "the single-GPU layer's numbers on the same tokens"."""
+    _decode_front_ok = False          # routing stays on the launches the exchange was built around
 
     def __init__(self, in_embed_dim=768, out_embed_dim=768, num_of_experts=4, num_selected=2, expert=None, args=None, group=None):
         if not isinstance(expert, nn.ModuleList):

@@ -74,6 +74,7 @@ class Route(NamedTuple):
 
 class MoeLayer(nn.Module):
     SEL = L.SEL_SOFTMAX               # selection rule of `_route` / `topk_expert` (include/csmoe.h)
+    _decode_front_ok = True           # False on the expert-parallel layers: the decode front end (ops.decode_route) is single-GPU
     WEIGHTS_XDTYPE = False            # the renormalised weights are x.dtype TENSORS upstream (a bf16 module multiplies them as such)
 
     @staticmethod
@@ -193,6 +194,12 @@ class MoeLayer(nn.Module):
         B, N, D = x.shape
         x2 = x.reshape(B * N, D)
         K, E = self.num_selected, self.gate.weight.shape[0]
+        if (self._decode_front_ok and getattr(self, "_pre_logits", None) is None
+                and ops.decode_front_applies(x2, self.gate.weight, K, False)):
+            # decode front end (competesmoe_amd.decode_front, no-grad calls of few rows): the routing and its bins in ONE launch;
+            # compute_moe meets the bins in ops.bin_tokens
+            logits, sm, idx, w = ops.decode_route(x2, self.gate.weight, K, self.SEL, x.dtype == torch.bfloat16)[:4]
+            return Route(logits.view(B, N, E), sm.view(B, N, E), idx.view(B, N, K), w.view(B, N, K))
         if getattr(self, "_pre_logits", None) is None and ops.gate_select_ok(x2, self.gate.weight, K):
             # one launch that reads x once: logits, softmax, top-K and the binning histogram (csmoe_gate_select)
             logits, sm, idx, w = GateSelect.apply(x2, self.gate.weight, K, self.SEL, x.dtype == torch.bfloat16)
@@ -209,7 +216,10 @@ class MoeLayer(nn.Module):
         K, E = self.num_selected, self.gate.weight.shape[0]
         x2 = x.reshape(B * N, D)
         rounded = self.WEIGHTS_XDTYPE and x.dtype == torch.bfloat16     # bf16 weights: the combine rounds w * y before the add
-        if (os.environ.get("CSMOE_FUSED_STEP", "1") != "0" and getattr(self, "_pre_logits", None) is None
+        # where the decode front end applies, `_route` + `compute_moe` run apart (no backward can follow: nothing is lost)
+        front = (self._decode_front_ok and getattr(self, "_pre_logits", None) is None
+                 and ops.decode_front_applies(x2, self.gate.weight, K, False))
+        if (not front and os.environ.get("CSMOE_FUSED_STEP", "1") != "0" and getattr(self, "_pre_logits", None) is None
                 and getattr(self, "_residual", None) is None and E == len(self.experts) and ops.gate_select_ok(x2, self.gate.weight, K)):
             tab, params = self._expert_table(E, x.dtype, x.device)
             out, logits, sm, idx, w = SparseMoEModules.apply(x2, self.gate.weight, K, self.SEL, x.dtype == torch.bfloat16, tab,

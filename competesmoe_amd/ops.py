@@ -128,6 +128,110 @@ def _route_hist_for(idx: torch.Tensor, E: int):
     return None
 
 
+# The route plan of the last decode front end (decode_route): (idx, its version counter, the Bins of that idx, and -- when the launch
+# also quantised its input -- x2, its version counter and (xq, xs)).  bin_tokens hands the Bins out for that very idx and launches
+# nothing; quantize_mxfp8 hands (xq, xs) out for that very x2 (the routed FFN and the shared expert both ask).  The rules are
+# _route_hist_for's: the held tensor keeps its storage alive, so an equal data_ptr can only be a view of it, and the version
+# counter shows any in-place edit since.  Every routing call (decode_route, gate_select, cosine_select) replaces or clears it.
+_ROUTE_PLAN = None
+
+
+def _route_plan_for(idx: torch.Tensor, E: int):
+    p = _ROUTE_PLAN
+    if p is None:
+        return None
+    ref, ver, bins = p[0], p[1], p[2]
+    if (idx.data_ptr() == ref.data_ptr() and idx.numel() == ref.numel() and idx._version == ver and ref._version == ver
+            and bins.E == E and idx.is_contiguous()):
+        return bins
+    return None
+
+
+def _quant_rows_for(x: torch.Tensor):
+    p = _ROUTE_PLAN
+    if p is None or p[3] is None:
+        return None
+    ref, ver, q = p[3], p[4], p[5]
+    if (x.dim() == 2 and x.data_ptr() == ref.data_ptr() and x.shape == ref.shape and x.dtype == ref.dtype and x._version == ver
+            and ref._version == ver and x.is_contiguous()):
+        return q
+    return None
+
+
+# Decode front end switch: route, bin and quantise the tokens of a forward-only call with at most decode_rows() routed rows in one
+# launch (decode_route) where the layer's gate is the plain bf16 linear map.  Off by default; seeded once from CSMOE_DECODE_FRONT;
+# competesmoe_amd.decode_front(on) sets it.
+_DECODE_FRONT = os.environ.get("CSMOE_DECODE_FRONT", "0") == "1"
+
+
+def decode_front(on: Optional[bool] = None) -> bool:
+    """Set (`on` given) and return the decode front end switch."""
+    global _DECODE_FRONT
+    if on is not None:
+        _DECODE_FRONT = bool(on)
+    return _DECODE_FRONT
+
+
+def decode_front_applies(x2: torch.Tensor, w_gate: torch.Tensor, K: int, want_quant: bool) -> bool:
+    """The layers' test: the switch is on, grad mode is off (the decode case: no autograd node can follow), the call has at most
+    decode_rows() routed rows, and decode_route takes the operands."""
+    return (_DECODE_FRONT and not torch.is_grad_enabled() and x2.dim() == 2 and 0 < x2.shape[0] * K <= _DECODE_ROWS
+            and decode_route_ok(x2, w_gate, K, want_quant))
+
+
+def decode_route_ok(x2: torch.Tensor, w_gate: torch.Tensor, K: int, want_quant: bool = False) -> bool:
+    """Does the decode front end (csmoe_decode_route) take these operands?  bf16, T * K <= 1024, K <= min(E, 64), E <= 256,
+    D % 8 == 0 (% 32 with the quantised rows), dense 16-byte aligned x2 and w_gate."""
+    if not (x2.is_cuda and x2.dim() == 2 and w_gate.dim() == 2 and x2.dtype == torch.bfloat16 and w_gate.dtype == torch.bfloat16
+            and w_gate.shape[1] == x2.shape[1]):
+        return False
+    T, D = x2.shape
+    return (bool(lib.csmoe_decode_route_ok(T, D, w_gate.shape[0], K, L.BF16, int(want_quant))) and x2.data_ptr() % 16 == 0
+            and w_gate.data_ptr() % 16 == 0 and x2.is_contiguous() and w_gate.is_contiguous())
+
+
+_ROUTE_SCRATCH = {}     # (device, stream) -> arrival counters of decode_route, zeroed by every call on its stream
+
+
+def decode_route(x2: torch.Tensor, w_gate: torch.Tensor, K: int, mode: int, round_sum_bf16: bool, param: float = 1.0,
+                 want_softmax: bool = True, want_quant: bool = False):
+    """(logits [T,E] bf16, softmax fp32 | None, idx [T,K] int32, w [T,K] fp32, Bins of idx, xq | None, xs | None) in ONE launch that
+    reads x2 once (csmoe_decode_route).  The call leaves its route plan behind: the bin_tokens call that sorts this `idx`
+    (unmodified) gets these Bins, and quantize_mxfp8 of this x2 gets (xq, xs), without a launch."""
+    _need_cuda(x2, w_gate)
+    _rows("decode_route", x2, w_gate)
+    T, D = x2.shape
+    E = w_gate.shape[0]
+    dev = x2.device
+    n = T * K
+    logits = torch.empty(T, E, dtype=x2.dtype, device=dev)
+    sm = torch.empty(T, E, dtype=torch.float32, device=dev) if want_softmax else None
+    idx = torch.empty(T, K, dtype=torch.int32, device=dev)
+    w = torch.empty(T, K, dtype=torch.float32, device=dev)
+    counts = torch.empty(E, dtype=torch.int32, device=dev)
+    offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
+    perm = torch.empty(n, dtype=torch.int32, device=dev)
+    slot_of = torch.empty(n, dtype=torch.int32, device=dev)
+    xq = torch.empty(T, D, dtype=torch.uint8, device=dev) if want_quant else None
+    xs = torch.empty(T, D // 32, dtype=torch.uint8, device=dev) if want_quant else None
+    stream = _stream()
+    need = int(lib.csmoe_decode_route_workspace_bytes(T))
+    ws = _ROUTE_SCRATCH.get((dev, stream))
+    if ws is None or ws.numel() < need:
+        ws = _ROUTE_SCRATCH[(dev, stream)] = torch.empty(max(need, int(lib.csmoe_decode_route_workspace_bytes(1024))),
+                                                         dtype=torch.uint8, device=dev)
+    with _timed("decode_route", T * D * x2.element_size()):
+        L.check(lib.csmoe_decode_route(x2.data_ptr(), w_gate.data_ptr(), T, D, E, K, mode, int(round_sum_bf16), float(param), _dt(x2),
+                                       logits.data_ptr(), _ptr(sm), idx.data_ptr(), w.data_ptr(), counts.data_ptr(),
+                                       offsets.data_ptr(), perm.data_ptr(), slot_of.data_ptr(), _ptr(xq), _ptr(xs), ws.data_ptr(),
+                                       stream), "decode_route")
+    bins = Bins(counts, offsets, perm, slot_of, n, E, K)
+    global _ROUTE_PLAN, _ROUTE_HIST
+    _ROUTE_HIST = None
+    _ROUTE_PLAN = (idx, idx._version, bins, x2, x2._version, (xq, xs)) if want_quant else (idx, idx._version, bins, None, 0, None)
+    return logits, sm, idx, w, bins, xq, xs
+
+
 def gate_select_ok(x2: torch.Tensor, w_gate: torch.Tensor, K: int) -> bool:
     """Does the one-pass router (csmoe_gate_select) take this shape?  CSMOE_FUSED_ROUTER=0 turns it off (A/B runs)."""
     if os.environ.get("CSMOE_FUSED_ROUTER", "1") == "0" or not x2.is_cuda:
@@ -156,8 +260,9 @@ def gate_select(x2: torch.Tensor, w_gate: torch.Tensor, K: int, mode: int, round
     with _timed("gate_select", T * D * x2.element_size()):
         L.check(lib.csmoe_gate_select(x2.data_ptr(), w_gate.data_ptr(), T, D, E, K, mode, int(round_sum_bf16), float(param), _dt(x2),
                                       logits.data_ptr(), _ptr(sm), idx.data_ptr(), w.data_ptr(), _ptr(hist), _stream()), "gate_select")
-    global _ROUTE_HIST
+    global _ROUTE_HIST, _ROUTE_PLAN
     _ROUTE_HIST = (idx, idx._version, hist, rows * K) if hist is not None else None
+    _ROUTE_PLAN = None
     return logits, sm, idx, w
 
 
@@ -198,8 +303,9 @@ def cosine_select(x2: torch.Tensor, w_red: torch.Tensor, emb: torch.Tensor, K: i
         L.check(lib.csmoe_cosine_select(x2.data_ptr(), w_red.data_ptr(), emb.data_ptr(), T, D, E, K, int(flags), float(temperature),
                                         float(eps), _dt(x2), reduced.data_ptr(), logits.data_ptr(), p.data_ptr(), idx.data_ptr(),
                                         w.data_ptr(), _ptr(hist), work.data_ptr(), _stream()), "cosine_select")
-    global _ROUTE_HIST
+    global _ROUTE_HIST, _ROUTE_PLAN
     _ROUTE_HIST = (idx, idx._version, hist, rows * K) if hist is not None else None
+    _ROUTE_PLAN = None
     return reduced, logits, p, idx, w, work[:1]
 
 
@@ -373,6 +479,10 @@ def bin_tokens(idx: torch.Tensor, E: int, hist=None) -> Bins:
     if idx.dtype != torch.int32:
         raise ValueError("csmoe: expert indices must be int32")
     idx = idx.contiguous()
+    if hist is None:
+        plan = _route_plan_for(idx, E)       # sorted already, in the launch that selected these ids (decode_route)
+        if plan is not None:
+            return plan
     n = idx.numel()
     K = idx.shape[-1]
     dev = idx.device
@@ -896,6 +1006,10 @@ def quantize_mxfp8(x: torch.Tensor, transpose: bool = False):
     (q [.., R, C], s [.., R, C/32]) or, transposed, along R (q [.., C, R], s [.., C, R/32]) -- csmoe_quantize_mxfp8."""
     _need_cuda(x)
     x = x.contiguous()
+    if not transpose:
+        done = _quant_rows_for(x)            # quantised already, in the launch that routed these rows (decode_route)
+        if done is not None:
+            return done
     lead = x.shape[:-2]
     R, C = x.shape[-2:]
     E = 1

@@ -143,6 +143,7 @@ class MoE(LoggingLayer, RegularizedLayer, OncePerIterLayer, nn.Module):
         self.register_forward_hook(MoE._leave_forward)
 
     _fuses_residual = False           # True on layers whose output IS one combine (smoe, competesmoe)
+    _decode_front_ok = True           # False on the expert-parallel layers: the decode front end (ops.decode_route) is single-GPU
 
     def _n_held_experts(self, n_experts: int) -> int:
         """Experts whose weights this module holds (all of them; pretrain/smoe_ep.py: this rank's share)."""
@@ -214,6 +215,13 @@ class MoE(LoggingLayer, RegularizedLayer, OncePerIterLayer, nn.Module):
         K, E = self.num_selected, self.w_gate.shape[0]
         if self._pre_logits is None and self._plain_gate() and op == torch.bfloat16:
             x2 = self.operand(x)
+            # decode front end (competesmoe_amd.decode_front, no-grad calls of few rows): routing, the bins and -- for the fp8 decode
+            # path -- the MXFP8 rows of x in ONE launch; ffn() / shared_ffn() meet them in ops.bin_tokens / ops.quantize_mxfp8
+            quant = self.fp8_experts and self.fp8_weight_cache and x2.shape[1] % 32 == 0
+            if self._decode_front_ok and ops.decode_front_applies(x2, self.w_gate, K, quant):
+                sd = self._stream_dtype if self._stream_dtype is not None else x_dtype
+                lg, sm, idx, w = ops.decode_route(x2, self.w_gate, K, mode, sd == torch.bfloat16, want_quant=quant)[:4]
+                return lg.view(*shp[:-1], E), w.view(*shp[:-1], K), idx.view(*shp[:-1], K), sm.view(*shp[:-1], E)
             if ops.gate_select_ok(x2, self.w_gate, K):
                 sd = self._stream_dtype if self._stream_dtype is not None else x_dtype
                 lg, sm, idx, w = GateSelect.apply(x2, self.w_gate, K, mode, sd == torch.bfloat16)

@@ -45,6 +45,7 @@ class EPPackedExperts:
     group -- and the sparse step over the exchange (EPFFNPacked / EPFFNPackedSlots).  Mixed in before the single-GPU layer class."""
     _ep_name = "smoe_ep"
     _fp8_experts_ok = False      # True on the layers whose sparse step has an fp8 form over the exchange (deepseek_ep.py)
+    _decode_front_ok = False     # routing stays on the launches the exchange was built around
 
     def __init__(self, *args, group=None, chunks: Optional[int] = None, direct: Optional[bool] = None, **kwargs):
         if not dist.is_initialized():

@@ -176,6 +176,30 @@ int csmoe_gate_select(const void* x, const void* w_gate, int T, int D, int E, in
                       float sel_param, int dtype, void* logits, float* softmax, int32_t* idx, float* w, int32_t* block_hist,
                       csmoe_stream_t stream);
 
+/* ---- decode front end ------------------------------------------------------------------------------------
+ * Route, bin and quantise the tokens of a decode call (T * K <= 1024 routed rows) in ONE launch that reads x once:
+ *   logits[T,E] (bf16), softmax[T,E] fp32 (nullable), idx[T,K], w[T,K]: the meaning of csmoe_gate_select.  The logits are the fp32
+ *     sum over D (v_mfma_f32_16x16x32_bf16, K dealt to four waves, partials added in wave order) rounded to bf16 once: within
+ *     2^-7 * max(|ref|, 2^-6) of csmoe_gate_logits, bit-identical from run to run (no float atomics).  softmax / idx / w are the bits
+ *     csmoe_router_select gives on THESE logits, for every rule 0..6 (`sel_param` / `round_sum_bf16` as there).
+ *   counts[E], offsets[E+1], perm[n], slot_of[n], n = T*K: csmoe_bin_tokens of this idx (ids outside [0, E) skipped as there).
+ *   xq[T,D], xs[T,D/32] uint8 (both or neither): the bytes csmoe_quantize_mxfp8 writes for x, rows orientation.
+ * `workspace`: csmoe_decode_route_workspace_bytes(T) bytes, 16-byte aligned (arrival counters of the in-launch hand-offs; zeroed by
+ * the call on `stream`, so the call is capturable and one buffer serves every call on that stream).
+ * Shapes it takes: csmoe_decode_route_ok(...) = 1: bf16, T >= 1, T*K <= 1024, 1 <= K <= min(E, 64), E <= 256, D % 8 == 0, and
+ * D % 32 == 0 with `want_quant`; x, w_gate and xq 16-byte aligned.
+ * Returns CSMOE_ERR_INVALID for bad arguments (K > E, an unknown rule, xq without xs, null operands) and CSMOE_ERR_UNSUPPORTED for a
+ * shape or alignment the rule rejects, both before any pointer is read and before anything is launched; T == 0 is CSMOE_OK.
+ * replaces `self.gate(x)` + `topk_expert` (moe_model/model/moe/smoe.py:42-44, moe.py:113-132), the E `torch.where` scans of
+ * compute_moe (moe.py:189-191), `F.linear(x, self.w_gate)` (moe_pretrain_model/layers/moe/moe.py:121) and cvmm_prepare_sel2's sort
+ * (moe_pretrain_model/layers/cvmm.py:580-593); the quantised rows have no counterpart upstream (the reference has no fp8). */
+int csmoe_decode_route_ok(int T, int D, int E, int K, int dtype, int want_quant);
+int64_t csmoe_decode_route_workspace_bytes(int T);
+int csmoe_decode_route(const void* x, const void* w_gate, int T, int D, int E, int K, int sel_mode, int round_sum_bf16,
+                       float sel_param, int dtype, void* logits, float* softmax, int32_t* idx, float* w, int32_t* counts,
+                       int32_t* offsets, int32_t* perm, int32_t* slot_of, void* xq, void* xs, void* workspace,
+                       csmoe_stream_t stream);
+
 /* ---- one-pass cosine router (XMoE) ----------------------------------------------------------------------
  * `inp_reduction(x)` + `_cosine` + `_make_finite` + softmax(logits / temperature) + `_keepTopk` (+ the counting pass of
  * csmoe_bin_tokens) of moe_model/model/moe/xmoe.py:80-91 / moe_pretrain_model/layers/moe/xmoe.py:143-162 in ONE launch that reads

@@ -25,11 +25,23 @@ the fp8 weight traffic counts one byte per element plus the scale bytes (1 / 32)
 launches on MXFP4 weight tables) beside the fp8 decode chain above, in the same process and rotation (the order of the two
 alternates with the repetition; cold, each chain reads its own copies, at least three of them).  The fp4 weight traffic counts
 half a byte per element plus the scale bytes: 0.516 of the fp8 table, the bound of the ratio.  The last columns are the bytes the
-two weight caches of a layer of these dimensions hold (both tables of all E experts, forward orientation)."""
+two weight caches of a layer of these dimensions hold (both tables of all E experts, forward orientation).
+
+--layer [--dtype bf16|fp8|fp4]: the WHOLE layer forward (router, binning, quantiser, expert GEMMs, combine) under torch.no_grad() with
+decode_rows on, the decode front end (competesmoe_amd.decode_front: csmoe_decode_route) off and on, alternating in one process; T in
+{1 .. 64}.  Layers: pretrain `smoe` at the headline dimensions (64 experts) and `deepseekv2` at BASELINE config 5's (128 routed + 2
+shared); bf16 modules, with `fp8_experts` + `fp8_weight_cache` (and `fp4_decode_weights`) for --dtype fp8 (fp4).  Cold: the
+repetitions rotate over copies of the layer and over inputs (so the routing changes).  Per cell: device time (events around the
+call) and host wall time per call (a batch of calls ended by one synchronise, divided by the batch size: the enqueue side is what
+the launch count buys), median +- half the interquartile range over `--reps` repetitions after 5 warm-ups, and the number of
+launching csmoe_* C calls per layer call in each arm (csmoe_bin_tokens_hist is two kernels, csmoe_bin_tokens three,
+csmoe_decode_route one kernel behind a memset node; torch's own kernels are not counted).  The "off" arm is the path without the
+switch, which tests/test_decode_front_path_gpu.py pins bit for bit against the "on" arm."""
 import argparse
 import os
 import statistics
 import sys
+import time
 
 import torch
 
@@ -267,13 +279,154 @@ def main_fp4(a):
     return lines
 
 
+LAYER_TS = (1, 2, 4, 8, 16, 32, 64)
+LAYERS = {"smoe": ("smoe", "headline", {}), "deepseekv2": ("deepseekv2", "config5", {"n_shared_experts": 2})}
+_HOST_QUERIES = ("_ok", "_bytes", "_rows", "_ints", "_floats", "_parts", "_cols", "_blocks", "_bound", "_ranges", "_error", "_version",
+                 "_info")
+
+
+class _CountingLib:
+    """ops.lib with every launching csmoe_* call counted by name."""
+
+    def __init__(self, lib):
+        self._lib, self.counts = lib, {}
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("csmoe_") or name.endswith(_HOST_QUERIES):
+            return fn
+
+        def counted(*a):
+            self.counts[name] = self.counts.get(name, 0) + 1
+            return fn(*a)
+        return counted
+
+
+def _count_launches(call):
+    real = ops.lib
+    ops.lib = proxy = _CountingLib(real)
+    try:
+        call()
+    finally:
+        ops.lib = real
+    return proxy.counts
+
+
+def _stats(v):
+    v = sorted(v)
+    q = statistics.quantiles(v, n=4)
+    return statistics.median(v), (q[2] - q[0]) / 2
+
+
+HOST_BATCH = 10      # calls per host-time batch
+
+
+def bench_layer(layers, D, Kl, T, reps, batch=HOST_BATCH):
+    """{arm: ((device ms, spread), (host ms per call, spread), launches)} of layer(x) with the front end off / on."""
+    import competesmoe_amd
+    g = torch.Generator().manual_seed(77 * T)
+    xs = [torch.randn(1, T, D, generator=g).bfloat16().to(DEV) for _ in range(8)]
+    dev = {False: [], True: []}
+    host = {False: [], True: []}
+    launches = {}
+    with torch.no_grad():
+        competesmoe_amd.decode_rows(max(64, T * Kl))
+        try:
+            for arm in (False, True):                             # also the warm-up of every copy's weight cache
+                competesmoe_amd.decode_front(arm)
+                for layer in layers:
+                    layer(xs[0])
+                launches[arm] = _count_launches(lambda: layers[0](xs[0]))
+            for r in range(reps + 5):
+                for j in range(2):
+                    arm = bool((r + j) % 2)
+                    competesmoe_amd.decode_front(arm)
+                    layer, x = layers[(2 * r + j) % len(layers)], xs[(2 * r + j) % len(xs)]
+                    e = timed(lambda: layer(x))
+                    if r >= 5:
+                        dev[arm].append(e)
+            torch.cuda.synchronize()
+            for r in range(reps + 2):
+                for j in range(2):
+                    arm = bool((r + j) % 2)
+                    competesmoe_amd.decode_front(arm)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for b in range(batch):
+                        layers[(r + b) % len(layers)](xs[(r + b) % len(xs)])
+                    torch.cuda.synchronize()
+                    if r >= 2:
+                        host[arm].append((time.perf_counter() - t0) * 1e3 / batch)
+        finally:
+            competesmoe_amd.decode_front(False)
+            competesmoe_amd.decode_rows(0)
+    return {arm: (_stats([a.elapsed_time(b) for a, b in dev[arm]]), _stats(host[arm]), launches[arm]) for arm in (False, True)}
+
+
+def main_layer(a):
+    import types
+    import torch.nn.functional as F
+    from competesmoe_amd.pretrain import get_moe
+    base = dict(stop_after=10, warm_up=0.0, rate_flip=1.0, max_compete_in_iter=8, balance_loss_coef=0.01, balance_loss_coef_comp=0.02,
+                router_loss_coef=0.03, router_theta=0.5, in_topk=False, hybrid=False, tribrid=False, balance_affinity=False,
+                is_cosine=False, is_norm_weight=False, norm_sigmoid=False, scale_weight=1.0, test_only=False)
+    if a.dtype != "bf16":
+        base.update(fp8_experts=True, fp8_weight_cache=True, fp4_decode_weights=a.dtype == "fp4")
+    lines = [f"device: {torch.cuda.get_device_name(0)}; whole layer forward, no_grad, decode_rows on; {a.dtype} experts; reps {a.reps}, "
+             f"host batches of {HOST_BATCH} calls; median +- half the interquartile range; K = {K}; ReLU", "",
+             "| layer | T | device ms off | device ms on | host ms/call off | host ms/call on | ahead by more than both spreads (device / host) | "
+             "csmoe calls off | csmoe calls on |", "|---|---|---|---|---|---|---|---|---|"]
+    for lname in a.layers.split(","):
+        name, dims, extra = LAYERS[lname]
+        D, FH, E = DIMS[dims]
+        n = 3 if E <= 64 else 2            # copies of the layer to rotate over
+        layers = []
+        for c in range(n):
+            torch.manual_seed(100 + c)
+            with torch.device(DEV):
+                layer = get_moe(name)(D, E, FH, n_heads=K, activation=F.relu, bias=False, log_interval=None,
+                                      args=types.SimpleNamespace(**base, **extra))
+            layers.append(layer.to(torch.bfloat16).eval())
+        for T in LAYER_TS:
+            res = bench_layer(layers, D, K, T, a.reps)
+            (d0, sd0), (h0, sh0), l0 = res[False]
+            (d1, sd1), (h1, sh1), l1 = res[True]
+            verdict = lambda x0, s0, x1, s1: "on" if x0 - x1 > s0 + s1 else ("off" if x1 - x0 > s0 + s1 else "neither")
+            fmt = lambda l: f"{sum(l.values())} (" + ", ".join(f"{k[6:]} {v}" for k, v in sorted(l.items())) + ")"
+            lines.append(f"| {lname} {a.dtype} | {T} | {d0:.4f} +- {sd0:.4f} | {d1:.4f} +- {sd1:.4f} | {h0:.4f} +- {sh0:.4f} | "
+                         f"{h1:.4f} +- {sh1:.4f} | {verdict(d0, sd0, d1, sd1)} / {verdict(h0, sh0, h1, sh1)} | {fmt(l0)} | {fmt(l1)} |")
+            print(lines[-1], flush=True)
+        del layers
+        if a.dtype != "bf16":
+            from competesmoe_amd import functional as Fn
+            Fn.fp8_weight_cache_clear()
+            Fn.fp4_weight_cache_clear()
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--layer", action="store_true", help="whole-layer forward, decode front end off against on")
+    ap.add_argument("--layers", default="smoe,deepseekv2", help="--layer: which of " + ", ".join(LAYERS))
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--dims", default=None, help="default: headline,siglip (bf16) / headline,config5 (fp8, fp4)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "fp4"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.layer:
+        if a.reps < 30:
+            ap.error("--layer: at least 30 repetitions")
+        for name in a.layers.split(","):
+            if name not in LAYERS:
+                ap.error(f"unknown layer '{name}'; choose from {', '.join(LAYERS)}")
+        text = "\n".join(main_layer(a)) + "\n"
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(text)
+        print(text)
+        return
     a.dims = a.dims or ("headline,config5" if a.dtype != "bf16" else "headline,siglip")
     for name in a.dims.split(","):
         if name not in DIMS:
