@@ -60,20 +60,14 @@ int k_quantize_mxfp8_tokens(const void* x, int64_t ldx, const int32_t* offsets, 
 int gg8f_wgrad(const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Bq, int64_t ldb, const void* Bs, int64_t ldbs,
                const int32_t* poff, int E, int Na, int Nb, void* const* c_ptrs, int64_t ldc, int out_dtype, int accumulate,
                const int32_t* xcd_order, hipStream_t st);
-bool gg_skinny8_shape_ok(int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc, int64_t ldcq, int64_t ldcs, int M, int N,
-                         int Kd, int quant_out);
-int gg_skinny8_rowspace(const void* Aq, int64_t lda, const void* As, int64_t ldas, const int32_t* src_rows, int src_div,
-                        const void* const* bq_ptrs, const void* const* bs_ptrs, int64_t ldb, int64_t ldbs,
-                        const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2,
-                        int64_t ldc, void* Cq, void* Cs, int64_t ldcq, int64_t ldcs, int epilogue, int act, hipStream_t st);
+bool gg_skinny_mx_shape_ok(int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc, int64_t ldcq, int64_t ldcs, int M, int N,
+                           int Kd, int quant_out);
+int gg_skinny_mx_rowspace(const SkinnyMxFmt& fmt, const void* Aq, int64_t lda, const void* As, int64_t ldas, const int32_t* src_rows,
+                          int src_div, const void* const* bq_ptrs, const void* const* bs_ptrs, int64_t ldb, int64_t ldbs,
+                          const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2,
+                          int64_t ldc, void* Cq, void* Cs, int64_t ldcq, int64_t ldcs, int epilogue, int act, hipStream_t st);
 int k_quantize_mxfp4(const void* const* x_ptrs, const void* x_single, int E, int64_t ldx, int R, int C, int in_dtype, int transpose,
                      void* q, void* s, hipStream_t st);
-bool gg_skinny4w_shape_ok(int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc, int64_t ldcq, int64_t ldcs, int M, int N,
-                          int Kd, int quant_out);
-int gg_skinny4w_rowspace(const void* Aq, int64_t lda, const void* As, int64_t ldas, const int32_t* src_rows, int src_div,
-                         const void* const* bq_ptrs, const void* const* bs_ptrs, int64_t ldb, int64_t ldbs,
-                         const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2,
-                         int64_t ldc, void* Cq, void* Cs, int64_t ldcq, int64_t ldcs, int epilogue, int act, hipStream_t st);
 int k_router_select(const void*, int, int, int, int, int, int, float, float*, int32_t*, float*, hipStream_t);
 int k_router_select_bwd(const void*, int, int, int, int, int, int, float, const float*, const int32_t*, const float*, const float*,
                         const float*, void*, hipStream_t);
@@ -944,18 +938,54 @@ int csmoe_dense_gemm_mxfp8_q(const void* Aq, int64_t lda, const void* As, int64_
 }
 
 
-// ---- few-row (decode) grouped GEMM on MXFP8 operands: gemm_skinny_fp8.hip.  As for csmoe_grouped_gemm_skinny, refusals
-// (CSMOE_ERR_UNSUPPORTED) come before any pointer is looked at and before anything is launched.
-static bool skinny8_epilogue_ok(int epilogue) {
+// ---- few-row (decode) grouped GEMM on MXFP8 token rows and MXFP8 / MXFP4 weight tables: gemm_skinny_mx.hip.  One body for both
+// entries, told apart by `f` (its name in every message; ldb, bytes of a weight row, >= Kd / f.k_per_byte).  As for
+// csmoe_grouped_gemm_skinny, refusals (CSMOE_ERR_UNSUPPORTED) come before any pointer is looked at and before anything is launched.
+static bool skinny_mx_epilogue_ok(int epilogue) {
   return epilogue == CSMOE_EPI_PLAIN || epilogue == CSMOE_EPI_BIAS || epilogue == CSMOE_EPI_BIAS_ACT;
+}
+
+static int skinny_mx_ok(const SkinnyMxFmt& f, int M, int N, int Kd, int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc,
+                        int64_t ldcq, int64_t ldcs, int epilogue, int quant_out) {
+  if (!skinny_mx_epilogue_ok(epilogue) || (quant_out && epilogue != CSMOE_EPI_BIAS_ACT)) return 0;
+  if (M < 0 || N <= 0 || Kd <= 0 || lda < Kd || ldb < Kd / f.k_per_byte || ldc < N || ldas < Kd / 32 || ldbs < Kd / 32) return 0;
+  if (quant_out && (ldcq < N || ldcs < N / 32)) return 0;
+  return gg_skinny_mx_shape_ok(lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, M, N, Kd, quant_out) ? 1 : 0;
+}
+
+static int skinny_mx_entry(const SkinnyMxFmt& f, const void* Aq, int64_t lda, const void* As, int64_t ldas, const int32_t* src_rows,
+                           int src_div, const void* const* bq_ptrs, const void* const* bs_ptrs, int64_t ldb, int64_t ldbs,
+                           const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C, void* C2,
+                           int64_t ldc, void* Cq, void* Cs, int64_t ldcq, int64_t ldcs, int epilogue, int act, csmoe_stream_t stream) {
+  CSMOE_CHECK_ARG(epilogue >= 0 && epilogue <= CSMOE_EPI_ACCUM && act >= 0 && act <= 5, "%s: bad epilogue/act", f.tag);
+  CSMOE_CHECK_ARG(!src_rows || src_div > 0, "%s: src_div = %d must be positive", f.tag, src_div);
+  CSMOE_CHECK_ARG(!Cq == !Cs, "%s: the quantised output needs both Cq and Cs", f.tag);
+  if (epilogue == CSMOE_EPI_ACCUM) return accum_unsupported(f.tag);
+  if (!skinny_mx_epilogue_ok(epilogue)) {
+    csmoe_set_error("%s: forward epilogues only (PLAIN, BIAS, BIAS_ACT), got %d", f.tag, epilogue);
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  CSMOE_CHECK_ARG(!Cq || epilogue == CSMOE_EPI_BIAS_ACT, "%s: Cq / Cs go with the BIAS_ACT epilogue", f.tag);
+  CSMOE_CHECK_ARG(E > 0 && M >= 0 && N > 0 && Kd > 0, "%s: bad shape E=%d M=%d N=%d Kd=%d", f.tag, E, M, N, Kd);
+  CSMOE_CHECK_ARG(lda >= Kd && ldb >= Kd / f.k_per_byte && ldc >= N && ldas >= Kd / 32 && ldbs >= Kd / 32 &&
+                  (!Cq || (ldcq >= N && ldcs >= N / 32)), "%s: leading dimension too small", f.tag);
+  CSMOE_CHECK_ARG(bq_ptrs && bs_ptrs && offsets, "%s: null pointer table / offsets", f.tag);
+  if (M == 0) return CSMOE_OK;
+  CSMOE_CHECK_ARG(Aq && As && (C || (epilogue == CSMOE_EPI_BIAS_ACT && (C2 || Cq))), "%s: null pointer", f.tag);
+  if (!gg_skinny_mx_shape_ok(lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, M, N, Kd, Cq != nullptr) || ((uintptr_t)Aq & 15) ||
+      ((uintptr_t)As & 3) || ((uintptr_t)C & 15) || ((uintptr_t)C2 & 15) || ((uintptr_t)Cq & 7)) {
+    csmoe_set_error("%s: needs Kd %% 128 == 0, N %% 8 == 0 (N %% 32 == 0 with Cq), lda, ldb%s multiples of 16, "
+                    "ldas, ldbs of 4, ldc, ldcq of 8, 16-byte aligned operands (As: 4-byte) and panels under 2 GiB "
+                    "(csmoe_%s_ok); M=%d N=%d Kd=%d", f.tag, f.k_per_byte == 1 ? "" : " (bytes of a packed row)", f.tag, M, N, Kd);
+    return CSMOE_ERR_UNSUPPORTED;
+  }
+  return gg_skinny_mx_rowspace(f, Aq, lda, As, ldas, src_rows, src_div, bq_ptrs, bs_ptrs, ldb, ldbs, bias_ptrs, offsets, E, M, N, Kd, C,
+                               C2, ldc, Cq, Cs, ldcq, ldcs, epilogue, act, (hipStream_t)stream);
 }
 
 int csmoe_grouped_gemm_skinny_mxfp8_ok(int M, int N, int Kd, int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc,
                                        int64_t ldcq, int64_t ldcs, int epilogue, int quant_out) {
-  if (!skinny8_epilogue_ok(epilogue) || (quant_out && epilogue != CSMOE_EPI_BIAS_ACT)) return 0;
-  if (M < 0 || N <= 0 || Kd <= 0 || lda < Kd || ldb < Kd || ldc < N || ldas < Kd / 32 || ldbs < Kd / 32) return 0;
-  if (quant_out && (ldcq < N || ldcs < N / 32)) return 0;
-  return gg_skinny8_shape_ok(lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, M, N, Kd, quant_out) ? 1 : 0;
+  return skinny_mx_ok(SKINNY_MXFP8, M, N, Kd, lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, epilogue, quant_out);
 }
 
 int csmoe_grouped_gemm_skinny_mxfp8(const void* Aq, int64_t lda, const void* As, int64_t ldas, const int32_t* src_rows, int src_div,
@@ -963,35 +993,27 @@ int csmoe_grouped_gemm_skinny_mxfp8(const void* Aq, int64_t lda, const void* As,
                                     const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C,
                                     void* C2, int64_t ldc, void* Cq, void* Cs, int64_t ldcq, int64_t ldcs, int epilogue, int act,
                                     csmoe_stream_t stream) {
-  CSMOE_CHECK_ARG(epilogue >= 0 && epilogue <= CSMOE_EPI_ACCUM && act >= 0 && act <= 5, "grouped_gemm_skinny_mxfp8: bad epilogue/act");
-  CSMOE_CHECK_ARG(!src_rows || src_div > 0, "grouped_gemm_skinny_mxfp8: src_div = %d must be positive", src_div);
-  CSMOE_CHECK_ARG(!Cq == !Cs, "grouped_gemm_skinny_mxfp8: the quantised output needs both Cq and Cs");
-  if (epilogue == CSMOE_EPI_ACCUM) return accum_unsupported("grouped_gemm_skinny_mxfp8");
-  if (!skinny8_epilogue_ok(epilogue)) {
-    csmoe_set_error("grouped_gemm_skinny_mxfp8: forward epilogues only (PLAIN, BIAS, BIAS_ACT), got %d", epilogue);
-    return CSMOE_ERR_UNSUPPORTED;
-  }
-  CSMOE_CHECK_ARG(!Cq || epilogue == CSMOE_EPI_BIAS_ACT, "grouped_gemm_skinny_mxfp8: Cq / Cs go with the BIAS_ACT epilogue");
-  CSMOE_CHECK_ARG(E > 0 && M >= 0 && N > 0 && Kd > 0, "grouped_gemm_skinny_mxfp8: bad shape E=%d M=%d N=%d Kd=%d", E, M, N, Kd);
-  CSMOE_CHECK_ARG(lda >= Kd && ldb >= Kd && ldc >= N && ldas >= Kd / 32 && ldbs >= Kd / 32 && (!Cq || (ldcq >= N && ldcs >= N / 32)),
-                  "grouped_gemm_skinny_mxfp8: leading dimension too small");
-  CSMOE_CHECK_ARG(bq_ptrs && bs_ptrs && offsets, "grouped_gemm_skinny_mxfp8: null pointer table / offsets");
-  if (M == 0) return CSMOE_OK;
-  CSMOE_CHECK_ARG(Aq && As && (C || (epilogue == CSMOE_EPI_BIAS_ACT && (C2 || Cq))), "grouped_gemm_skinny_mxfp8: null pointer");
-  if (!gg_skinny8_shape_ok(lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, M, N, Kd, Cq != nullptr) || ((uintptr_t)Aq & 15) ||
-      ((uintptr_t)As & 3) || ((uintptr_t)C & 15) || ((uintptr_t)C2 & 15) || ((uintptr_t)Cq & 7)) {
-    csmoe_set_error("grouped_gemm_skinny_mxfp8: needs Kd %% 128 == 0, N %% 8 == 0 (N %% 32 == 0 with Cq), lda, ldb multiples of 16, "
-                    "ldas, ldbs of 4, ldc, ldcq of 8, 16-byte aligned operands (As: 4-byte) and panels under 2 GiB "
-                    "(csmoe_grouped_gemm_skinny_mxfp8_ok); M=%d N=%d Kd=%d", M, N, Kd);
-    return CSMOE_ERR_UNSUPPORTED;
-  }
-  return gg_skinny8_rowspace(Aq, lda, As, ldas, src_rows, src_div, bq_ptrs, bs_ptrs, ldb, ldbs, bias_ptrs, offsets, E, M, N, Kd, C, C2,
-                             ldc, Cq, Cs, ldcq, ldcs, epilogue, act, (hipStream_t)stream);
+  return skinny_mx_entry(SKINNY_MXFP8, Aq, lda, As, ldas, src_rows, src_div, bq_ptrs, bs_ptrs, ldb, ldbs, bias_ptrs, offsets, E, M, N, Kd,
+                         C, C2, ldc, Cq, Cs, ldcq, ldcs, epilogue, act, stream);
+}
+
+int csmoe_grouped_gemm_skinny_mxfp4w_ok(int M, int N, int Kd, int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc,
+                                        int64_t ldcq, int64_t ldcs, int epilogue, int quant_out) {
+  return skinny_mx_ok(SKINNY_MXFP4W, M, N, Kd, lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, epilogue, quant_out);
+}
+
+int csmoe_grouped_gemm_skinny_mxfp4w(const void* Aq, int64_t lda, const void* As, int64_t ldas, const int32_t* src_rows, int src_div,
+                                     const void* const* bq_ptrs, const void* const* bs_ptrs, int64_t ldb, int64_t ldbs,
+                                     const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C,
+                                     void* C2, int64_t ldc, void* Cq, void* Cs, int64_t ldcq, int64_t ldcs, int epilogue, int act,
+                                     csmoe_stream_t stream) {
+  return skinny_mx_entry(SKINNY_MXFP4W, Aq, lda, As, ldas, src_rows, src_div, bq_ptrs, bs_ptrs, ldb, ldbs, bias_ptrs, offsets, E, M, N, Kd,
+                         C, C2, ldc, Cq, Cs, ldcq, ldcs, epilogue, act, stream);
 }
 
 
-// ---- MXFP4 weights for the W4A8 decode path: the quantiser (fp8_quant.hip) and gemm_skinny_fp4.hip.  Same refusal rules as the
-// fp8 twins: CSMOE_ERR_UNSUPPORTED before any pointer is looked at and before anything is launched.
+// ---- MXFP4 weights for the W4A8 decode path: the quantiser (fp8_quant.hip; the GEMM is csmoe_grouped_gemm_skinny_mxfp4w above).
+// Same refusal rules as the fp8 twin: CSMOE_ERR_UNSUPPORTED before any pointer is looked at and before anything is launched.
 int csmoe_quantize_mxfp4(const void* x, const void* const* x_ptrs, int E, int64_t ldx, int R, int C, int dtype, int transpose,
                          void* q, void* s, csmoe_stream_t stream) {
   CSMOE_CHECK_ARG(dtype_ok(dtype) && E >= 1 && R >= 0 && C >= 0, "quantize_mxfp4: bad arguments");
@@ -1009,45 +1031,6 @@ int csmoe_quantize_mxfp4(const void* x, const void* const* x_ptrs, int E, int64_
   }
   if ((uintptr_t)q & 15) { csmoe_set_error("quantize_mxfp4: q must be 16-byte aligned (a block is one 16-byte store)"); return CSMOE_ERR_UNSUPPORTED; }
   return k_quantize_mxfp4(x_ptrs, x, E, ldx, R, C, dtype, transpose, q, s, (hipStream_t)stream);
-}
-
-int csmoe_grouped_gemm_skinny_mxfp4w_ok(int M, int N, int Kd, int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc,
-                                       int64_t ldcq, int64_t ldcs, int epilogue, int quant_out) {
-  if (!skinny8_epilogue_ok(epilogue) || (quant_out && epilogue != CSMOE_EPI_BIAS_ACT)) return 0;
-  if (M < 0 || N <= 0 || Kd <= 0 || lda < Kd || ldb < Kd / 2 || ldc < N || ldas < Kd / 32 || ldbs < Kd / 32) return 0;
-  if (quant_out && (ldcq < N || ldcs < N / 32)) return 0;
-  return gg_skinny4w_shape_ok(lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, M, N, Kd, quant_out) ? 1 : 0;
-}
-
-int csmoe_grouped_gemm_skinny_mxfp4w(const void* Aq, int64_t lda, const void* As, int64_t ldas, const int32_t* src_rows, int src_div,
-                                    const void* const* bq_ptrs, const void* const* bs_ptrs, int64_t ldb, int64_t ldbs,
-                                    const void* const* bias_ptrs, const int32_t* offsets, int E, int M, int N, int Kd, void* C,
-                                    void* C2, int64_t ldc, void* Cq, void* Cs, int64_t ldcq, int64_t ldcs, int epilogue, int act,
-                                    csmoe_stream_t stream) {
-  CSMOE_CHECK_ARG(epilogue >= 0 && epilogue <= CSMOE_EPI_ACCUM && act >= 0 && act <= 5, "grouped_gemm_skinny_mxfp4w: bad epilogue/act");
-  CSMOE_CHECK_ARG(!src_rows || src_div > 0, "grouped_gemm_skinny_mxfp4w: src_div = %d must be positive", src_div);
-  CSMOE_CHECK_ARG(!Cq == !Cs, "grouped_gemm_skinny_mxfp4w: the quantised output needs both Cq and Cs");
-  if (epilogue == CSMOE_EPI_ACCUM) return accum_unsupported("grouped_gemm_skinny_mxfp4w");
-  if (!skinny8_epilogue_ok(epilogue)) {
-    csmoe_set_error("grouped_gemm_skinny_mxfp4w: forward epilogues only (PLAIN, BIAS, BIAS_ACT), got %d", epilogue);
-    return CSMOE_ERR_UNSUPPORTED;
-  }
-  CSMOE_CHECK_ARG(!Cq || epilogue == CSMOE_EPI_BIAS_ACT, "grouped_gemm_skinny_mxfp4w: Cq / Cs go with the BIAS_ACT epilogue");
-  CSMOE_CHECK_ARG(E > 0 && M >= 0 && N > 0 && Kd > 0, "grouped_gemm_skinny_mxfp4w: bad shape E=%d M=%d N=%d Kd=%d", E, M, N, Kd);
-  CSMOE_CHECK_ARG(lda >= Kd && ldb >= Kd / 2 && ldc >= N && ldas >= Kd / 32 && ldbs >= Kd / 32 && (!Cq || (ldcq >= N && ldcs >= N / 32)),
-                  "grouped_gemm_skinny_mxfp4w: leading dimension too small");
-  CSMOE_CHECK_ARG(bq_ptrs && bs_ptrs && offsets, "grouped_gemm_skinny_mxfp4w: null pointer table / offsets");
-  if (M == 0) return CSMOE_OK;
-  CSMOE_CHECK_ARG(Aq && As && (C || (epilogue == CSMOE_EPI_BIAS_ACT && (C2 || Cq))), "grouped_gemm_skinny_mxfp4w: null pointer");
-  if (!gg_skinny4w_shape_ok(lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, M, N, Kd, Cq != nullptr) || ((uintptr_t)Aq & 15) ||
-      ((uintptr_t)As & 3) || ((uintptr_t)C & 15) || ((uintptr_t)C2 & 15) || ((uintptr_t)Cq & 7)) {
-    csmoe_set_error("grouped_gemm_skinny_mxfp4w: needs Kd %% 128 == 0, N %% 8 == 0 (N %% 32 == 0 with Cq), lda, ldb (bytes of a packed row) multiples of 16, "
-                    "ldas, ldbs of 4, ldc, ldcq of 8, 16-byte aligned operands (As: 4-byte) and panels under 2 GiB "
-                    "(csmoe_grouped_gemm_skinny_mxfp4w_ok); M=%d N=%d Kd=%d", M, N, Kd);
-    return CSMOE_ERR_UNSUPPORTED;
-  }
-  return gg_skinny4w_rowspace(Aq, lda, As, ldas, src_rows, src_div, bq_ptrs, bs_ptrs, ldb, ldbs, bias_ptrs, offsets, E, M, N, Kd, C, C2,
-                             ldc, Cq, Cs, ldcq, ldcs, epilogue, act, (hipStream_t)stream);
 }
 
 

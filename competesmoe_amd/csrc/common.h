@@ -68,6 +68,11 @@ inline int64_t rowspace_tiles(int M, int E, int N, int BMt, int BNt) {
 // upper bound of the 16-row blocks of a decode launch: sum_e ceil(count_e / 16) <= min(M, M / 16 + E) whatever the counts are
 inline int64_t skinny_row_blocks(int M, int E) { return M < (int64_t)M / 16 + E ? M : (int64_t)M / 16 + E; }
 
+// the two weight formats of the MX decode GEMM (gemm_skinny_mx.hip) as its entries see them: the entry's name in messages and
+// profile tags, and the weight elements per byte of a table row (ldb >= Kd / k_per_byte)
+struct SkinnyMxFmt { const char* tag; int k_per_byte; };
+inline constexpr SkinnyMxFmt SKINNY_MXFP8{"grouped_gemm_skinny_mxfp8", 1}, SKINNY_MXFP4W{"grouped_gemm_skinny_mxfp4w", 2};
+
 // grid-stride row kernels: 4 rows (waves) per workgroup; caps of 2048..16384 workgroups measure the same (tools/hbm_bench.py)
 inline int stride_grid(int rows) {
   const int g = (rows + 3) / 4;

@@ -6,7 +6,7 @@
 //   transposed: x [R, C] -> q [C, R] u8, s [C, R/32] u8          (blocks along dim 0: the same weights for the transposed product)
 // Inputs bf16 or fp32 (the pretrain stack's fp32 master weights are quantised directly: no bf16 cast pass).
 // The scale-and-convert device code (e8m0_of_amax, inv_scale_of, sat448, pack4_e4m3) lives in mx_quant.h, shared with the fused
-// quantised output of gemm_skinny_fp8.hip.  The MXFP4 weight quantiser (csmoe_quantize_mxfp4: e2m1 elements, two per byte, the same
+// quantised output of gemm_skinny_mx.hip.  The MXFP4 weight quantiser (csmoe_quantize_mxfp4: e2m1 elements, two per byte, the same
 // e8m0 block scales with emax = 2) is the rows / transposed pair once more, at the end of the kernels.
 #include "mx_quant.h"
 #include <algorithm>

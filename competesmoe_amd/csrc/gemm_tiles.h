@@ -188,7 +188,7 @@ __device__ __forceinline__ void dma_setup(unsigned (&vbase)[NJ], int (&aux)[NJ],
   }
 }
 
-// ---- the decode kernels (gemm_skinny.hip, gemm_skinny_fp8.hip): the NW waves' partial 16 x SLAB tiles (acc[NB]) meet in LDS at
+// ---- the decode kernels (gemm_skinny.hip, gemm_skinny_mx.hip): the NW waves' partial 16 x SLAB tiles (acc[NB]) meet in LDS at
 // red_ (NW tiles of 16 rows x LDW floats) ...
 #define SKINNY_STORE_PARTIAL(red_, acc_)                                                                               \
   {                                                                                                                    \

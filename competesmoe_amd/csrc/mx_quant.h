@@ -1,6 +1,6 @@
 // The scale-and-convert step of the MXFP8 quantiser (OCP Microscaling: shared exponent = floor(log2(amax)) - emax_elem,
 // emax(e4m3) = 8; elements = round-to-nearest-even(x * 2^-shared), saturated at +-448, NaN kept).  One copy for every kernel that
-// writes MXFP8: the quantisers of fp8_quant.hip and the fused quantised outputs of gemm_skinny_fp8.hip / gemm_skinny_fp4.hip, which must
+// writes MXFP8: the quantisers of fp8_quant.hip and the fused quantised output of gemm_skinny_mx.hip, which must
 // agree byte for byte.  The MXFP4 step of the weight quantiser follows it.
 #pragma once
 #include "common.h"
@@ -26,7 +26,7 @@ __device__ __forceinline__ unsigned pack4_e4m3(float a, float b, float c, float 
   return (unsigned)w;
 }
 
-// ---- MXFP4 (weights of the W4A8 decode path, gemm_skinny_fp4.hip) -----------------------------------------------------------------
+// ---- MXFP4 (weights of the W4A8 decode path, gemm_skinny_mx.hip) ------------------------------------------------------------------
 // OCP e2m1 elements (sign, magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6), emax(e2m1) = 2: shared exponent = floor(log2(amax)) - 2, so the
 // scaled block lies in (-8, 8); elements = round-to-nearest-even(x * 2^-shared) on that grid, saturated at +-6.  Plain compares: the
 // seven midpoints of the grid, a tie going to the code with the even mantissa bit (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2,

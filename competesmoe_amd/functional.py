@@ -5,6 +5,7 @@ Reference parity notes are on each class (file:line of the reference code whose 
 """
 from __future__ import annotations
 
+import collections
 import os
 import threading
 import weakref
@@ -1296,25 +1297,27 @@ def fp8_weight_cache_clear():
     _FP8_WCACHE.clear()
 
 
-def _fp8_wcache_put(key, t: torch.Tensor, first: bool, out) -> None:
-    if first:                                                  # first entry under this key: it goes when its owner is freed
-        import weakref
+def _wcache(cache: dict, t: torch.Tensor, build, both: bool = False):
+    """The tables of master tensor `t` in the weight cache `cache` (_FP8_WCACHE, _FP4_WCACHE): the entry (version, tables) under t's
+    storage, shape and dtype if it is of t's present version (`both`: and no forward-only entry), else `build(t)`, which replaces
+    it."""
+    key = (t.data_ptr(), tuple(t.shape), t.dtype)
+    hit = cache.get(key)
+    if hit is not None and hit[0] == t._version and not (both and hit[1][0] is None):
+        return hit[1]
+    out = build(t)
+    if hit is None:                                            # first entry under this key: it goes when its owner is freed
         owner = t._base if t._base is not None else t          # `keys_shared[0]` is a fresh view per call: the parameter owns the entry
-        weakref.finalize(owner, _FP8_WCACHE.pop, key, None)
-    _FP8_WCACHE[key] = (t._version, out)
+        weakref.finalize(owner, cache.pop, key, None)
+    cache[key] = (t._version, out)
+    return out
 
 
 def _quantize_weight_both(t: torch.Tensor, cache: bool):
     """((q, s) blocks along the last dim, (qt, st) blocks along the second-to-last) of a master weight tensor [.., R, C]."""
     if not cache:
         return ops.quantize_mxfp8_both(t)
-    key = (t.data_ptr(), tuple(t.shape), t.dtype)
-    hit = _FP8_WCACHE.get(key)
-    if hit is not None and hit[0] == t._version and hit[1][0] is not None:
-        return hit[1]
-    out = ops.quantize_mxfp8_both(t)                           # also replaces a forward-only entry (_quantize_weight_fwd)
-    _fp8_wcache_put(key, t, hit is None, out)
-    return out
+    return _wcache(_FP8_WCACHE, t, ops.quantize_mxfp8_both, both=True)       # also replaces a forward-only entry (_quantize_weight_fwd)
 
 
 def _quantize_weight_fwd(t: torch.Tensor, cache: bool):
@@ -1324,13 +1327,11 @@ def _quantize_weight_fwd(t: torch.Tensor, cache: bool):
     of this parameter version, which a later call that needs both orientations replaces."""
     if not cache:
         return ops.quantize_mxfp8(t, transpose=True)
-    key = (t.data_ptr(), tuple(t.shape), t.dtype)
-    hit = _FP8_WCACHE.get(key)
-    if hit is not None and hit[0] == t._version:
-        return hit[1][1]
-    fwd = ops.quantize_mxfp8(t, transpose=True)
-    _fp8_wcache_put(key, t, hit is None, (None, fwd))
-    return fwd
+    return _wcache(_FP8_WCACHE, t, _fwd_only_entry)[1]
+
+
+def _fwd_only_entry(t: torch.Tensor):
+    return None, ops.quantize_mxfp8(t, transpose=True)
 
 
 def _wgrad_fp8_out_dtype(pd):
@@ -1371,34 +1372,6 @@ def _dense_wgrad_fp8(at, ats, bt, bts, poff, M: int, out_dtype) -> torch.Tensor:
     return ops.dense_colsum(part.view(P, Na * Nb), out_dtype=out_dtype).view(Na, Nb)
 
 
-def _fp8_decode_ok(n: int, D: int, F: int, Dout: int) -> bool:
-    """Both GEMMs of a forward-only fp8 call with n rows fit csmoe_grouped_gemm_skinny_mxfp8 (the first with its quantised output).
-    Their operands are tensors the path allocates itself (contiguous, aligned), so the shapes decide; D % 128 == 0 also gives the
-    quantiser of x its D % 32 == 0."""
-    return (ops.grouped_gemm_skinny_mxfp8_ok(n, F, D, epilogue=L.EPI_BIAS_ACT, quant_out=True)
-            and ops.grouped_gemm_skinny_mxfp8_ok(n, Dout, F, epilogue=L.EPI_PLAIN))
-
-
-def _ffn_fp8_decode(x2, w1, w2, b1, act: int, offsets, src_rows, src_div: int):
-    """The two expert GEMMs of a forward-only fp8 call with few rows, on the weight-streaming kernel (csrc/gemm_skinny_fp8.hip):
-    the T token rows are quantised where they lie (per row: quantise-then-gather is gather-then-quantise, so there is no dispatch
-    copy), GEMM 1 gathers through `src_rows` and writes only the MXFP8 form of the activated output (no pre-activation, no bf16
-    hact, no quantiser launch), GEMM 2 reads it.  w1 [E, D, F] / w2 [E, F, Dout] (or 2-D: one expert) are masters whose forward
-    tables come from the weight cache (_quantize_weight_fwd); b1 [E, F] / [F] or None.  Returns y [M, Dout] bf16 in binned order."""
-    b1_ptrs = None
-    if b1 is not None:
-        b_op = b1.to(torch.bfloat16).contiguous()              # alive until GEMM 1 is enqueued
-        b1_ptrs = ops.ptr_table(b_op, b_op.numel() // b_op.shape[-1], b_op.shape[-1] * 2)
-    xq, xsc = ops.quantize_mxfp8(x2)
-    kq, ks = _quantize_weight_fwd(w1, True)                    # [E, F, D], scales along D
-    vq, vs = _quantize_weight_fwd(w2, True)                    # [E, Dout, F], scales along F
-    if kq.dim() == 2:
-        kq, ks, vq, vs = kq[None], ks[None], vq[None], vs[None]
-    _, _, hq, hs = ops.grouped_gemm_skinny_mxfp8(xq, xsc, kq, ks, offsets, bias_ptrs=b1_ptrs, epilogue=L.EPI_BIAS_ACT, act=act,
-                                                 want_c=False, want_q=True, src_rows=src_rows, src_div=src_div)
-    return ops.grouped_gemm_skinny_mxfp8(hq, hs, vq, vs, offsets)
-
-
 # MXFP4 forward tables for the W4A8 decode path (`args.fp4_decode_weights`): a cache of their own, keyed like _FP8_WCACHE (storage
 # and version counter), so a decode-only process holds the 4-bit tables alone (0.516 of the fp8 forward tables) and never builds an
 # fp8 entry; a training call on the same parameters goes through _FP8_WCACHE as always.
@@ -1412,41 +1385,51 @@ def fp4_weight_cache_clear():
 def _quantize_weight_fwd4(t: torch.Tensor):
     """The MXFP4 forward table (q [.., C, R/2], s [.., C, R/32]) of a master weight tensor [.., R, C] (blocks along R, the forward
     product's reduction dim), quantised once per parameter version."""
-    key = (t.data_ptr(), tuple(t.shape), t.dtype)
-    hit = _FP4_WCACHE.get(key)
-    if hit is not None and hit[0] == t._version:
-        return hit[1]
-    out = ops.quantize_mxfp4(t, transpose=True)
-    if hit is None:                                            # first entry under this key: it goes when its owner is freed
-        import weakref
-        owner = t._base if t._base is not None else t
-        weakref.finalize(owner, _FP4_WCACHE.pop, key, None)
-    _FP4_WCACHE[key] = (t._version, out)
-    return out
+    return _wcache(_FP4_WCACHE, t, _mxfp4_table)
 
 
-def _fp4_decode_ok(n: int, D: int, F: int, Dout: int) -> bool:
-    """_fp8_decode_ok for csmoe_grouped_gemm_skinny_mxfp4w: both GEMMs of a forward-only call with n rows fit it."""
-    return (ops.grouped_gemm_skinny_mxfp4w_ok(n, F, D, epilogue=L.EPI_BIAS_ACT, quant_out=True)
-            and ops.grouped_gemm_skinny_mxfp4w_ok(n, Dout, F, epilogue=L.EPI_PLAIN))
+def _mxfp4_table(t: torch.Tensor):
+    return ops.quantize_mxfp4(t, transpose=True)
 
 
-def _ffn_fp4_decode(x2, w1, w2, b1, act: int, offsets, src_rows, src_div: int):
-    """_ffn_fp8_decode with MXFP4 weight tables (W4A8, csrc/gemm_skinny_fp4.hip): the token rows are quantised to MXFP8 where they
-    lie, GEMM 1 gathers through `src_rows` and writes only the MXFP8 form of the activated output, GEMM 2 reads it; the weights are
-    the 4-bit forward tables of _quantize_weight_fwd4.  Same arguments and result."""
-    b1_ptrs = None
-    if b1 is not None:
-        b_op = b1.to(torch.bfloat16).contiguous()              # alive until GEMM 1 is enqueued
-        b1_ptrs = ops.ptr_table(b_op, b_op.numel() // b_op.shape[-1], b_op.shape[-1] * 2)
+# The weight formats of the decode path (csrc/gemm_skinny_mx.hip): the GEMM's shape query, the GEMM, and the cached forward tables of
+# a master tensor.  MXFP8 tables [E, N, Kd]; MXFP4 tables (W4A8) [E, N, Kd / 2]; scales [E, N, Kd / 32] along the reduction dim in both
+_MxDecode = collections.namedtuple("_MxDecode", "ok gemm tables")
+_DECODE_FP8 = _MxDecode(ops.grouped_gemm_skinny_mxfp8_ok, ops.grouped_gemm_skinny_mxfp8, lambda t: _quantize_weight_fwd(t, True))
+_DECODE_FP4 = _MxDecode(ops.grouped_gemm_skinny_mxfp4w_ok, ops.grouped_gemm_skinny_mxfp4w, _quantize_weight_fwd4)
+
+
+def _mx_decode_ok(fmt: _MxDecode, n: int, D: int, F: int, Dout: int) -> bool:
+    """Both GEMMs of a forward-only fp8 call with n rows fit the decode GEMM of `fmt` (the first with its quantised output).  Their
+    operands are tensors the path allocates itself (contiguous, aligned), so the shapes decide; D % 128 == 0 also gives the
+    quantiser of x its D % 32 == 0."""
+    return fmt.ok(n, F, D, epilogue=L.EPI_BIAS_ACT, quant_out=True) and fmt.ok(n, Dout, F, epilogue=L.EPI_PLAIN)
+
+
+def _mx_decode_format(n: int, D: int, F: int, Dout: int, fp4_decode: bool):
+    """The weight format a forward-only fp8 call with n rows decodes on, or None where the decode path does not take it: the path
+    needs the fp8 rule to pass; with `fp4_decode` (args.fp4_decode_weights) the same call runs on MXFP4 weight tables where that
+    rule passes too."""
+    if not _mx_decode_ok(_DECODE_FP8, n, D, F, Dout):
+        return None
+    return _DECODE_FP4 if fp4_decode and _mx_decode_ok(_DECODE_FP4, n, D, F, Dout) else _DECODE_FP8
+
+
+def _ffn_mx_decode(fmt: _MxDecode, x2, w1, w2, b1, act: int, offsets, src_rows, src_div: int):
+    """The two expert GEMMs of a forward-only fp8 call with few rows, on the weight-streaming kernel (csrc/gemm_skinny_mx.hip):
+    the T token rows are quantised to MXFP8 where they lie (per row: quantise-then-gather is gather-then-quantise, so there is no
+    dispatch copy), GEMM 1 gathers through `src_rows` and writes only the MXFP8 form of the activated output (no pre-activation, no
+    bf16 hact, no quantiser launch), GEMM 2 reads it.  w1 [E, D, F] / w2 [E, F, Dout] (or 2-D: one expert) are masters whose forward
+    tables come from the weight cache of `fmt`; b1 [E, F] / [F] or None.  Returns y [M, Dout] bf16 in binned order."""
+    b_op, b1_ptrs = _fp8_bias_table(b1)                        # b_op: alive until GEMM 1 is enqueued
     xq, xsc = ops.quantize_mxfp8(x2)
-    kq, ks = _quantize_weight_fwd4(w1)                         # [E, F, D/2], scales along D
-    vq, vs = _quantize_weight_fwd4(w2)                         # [E, Dout, F/2], scales along F
+    kq, ks = fmt.tables(w1)                                    # [E, F, D (/ 2)], scales along D
+    vq, vs = fmt.tables(w2)                                    # [E, Dout, F (/ 2)], scales along F
     if kq.dim() == 2:
         kq, ks, vq, vs = kq[None], ks[None], vq[None], vs[None]
-    _, _, hq, hs = ops.grouped_gemm_skinny_mxfp4w(xq, xsc, kq, ks, offsets, bias_ptrs=b1_ptrs, epilogue=L.EPI_BIAS_ACT, act=act,
-                                                  want_c=False, want_q=True, src_rows=src_rows, src_div=src_div)
-    return ops.grouped_gemm_skinny_mxfp4w(hq, hs, vq, vs, offsets)
+    _, _, hq, hs = fmt.gemm(xq, xsc, kq, ks, offsets, bias_ptrs=b1_ptrs, epilogue=L.EPI_BIAS_ACT, act=act, want_c=False, want_q=True,
+                            src_rows=src_rows, src_div=src_div)
+    return fmt.gemm(hq, hs, vq, vs, offsets)
 
 
 def _fp8_rows_and_weights(x2, w):
@@ -1459,11 +1442,12 @@ def _fp8_rows_and_weights(x2, w):
 
 
 def _fp8_bias_table(bias):
-    """(bf16 copy of the packed `bias` [E, F], its pointer table), or (None, None)."""
+    """(bf16 copy of the packed `bias` [E, F] -- or [F]: one expert --, its pointer table), or (None, None).  The table points into
+    the copy: keep that alive until the GEMM that reads the table is enqueued."""
     if bias is None:
         return None, None
     b_op = bias.to(torch.bfloat16).contiguous()
-    return b_op, ops.ptr_table(b_op, bias.shape[0], bias.shape[1] * 2)
+    return b_op, ops.ptr_table(b_op, b_op.numel() // b_op.shape[-1], b_op.shape[-1] * 2)
 
 
 class MoEFFNPackedFP8(_ForwardAware):
@@ -1474,8 +1458,8 @@ class MoEFFNPackedFP8(_ForwardAware):
     and dy / dh quantised along the token dim inside every expert's rows (`csmoe_quantize_mxfp8_tokens`; dy and dh in the same pass
     as their row orientation); everything else the backward returns is unchanged, bit for bit.  Master weights (fp32 or bf16) are quantised directly, once per use and orientation -- there is no
     bf16 operand copy -- or, with `cache`, once per parameter version (_quantize_weight_both).  A call that needs no backward, with
-    `cache` and at most ops.decode_rows() routed rows, takes the decode path (_ffn_fp8_decode; with `fp4_decode` the W4A8 form
-    _ffn_fp4_decode on MXFP4 weight tables).  No counterpart upstream (the
+    `cache` and at most ops.decode_rows() routed rows, takes the decode path (_ffn_mx_decode; with `fp4_decode` its W4A8 form on
+    MXFP4 weight tables).  No counterpart upstream (the
     reference has no fp8): checked against oracle/mxfp8.py, tests/test_fp8_gpu.py, tests/test_decode_fp8_path_gpu.py."""
 
     @staticmethod
@@ -1485,13 +1469,11 @@ class MoEFFNPackedFP8(_ForwardAware):
         E, D, F = keys.shape
         T = x2.shape[0]
         bins = ops.bin_tokens(idx, E)
-        if (not _needs_backward(ctx) and cache and 0 < bins.n <= ops.decode_rows()
-                and _fp8_decode_ok(bins.n, D, F, values.shape[2])):
-            # `fp4_decode` (args.fp4_decode_weights): the same call on MXFP4 weight tables, where the fp8 decode path would run
-            if fp4_decode and _fp4_decode_ok(bins.n, D, F, values.shape[2]):
-                y = _ffn_fp4_decode(x2, keys, values, bias, act, bins.offsets, bins.perm, bins.K)
-            else:
-                y = _ffn_fp8_decode(x2, keys, values, bias, act, bins.offsets, bins.perm, bins.K)
+        fmt = None
+        if not _needs_backward(ctx) and cache and 0 < bins.n <= ops.decode_rows():
+            fmt = _mx_decode_format(bins.n, D, F, values.shape[2], fp4_decode)
+        if fmt is not None:
+            y = _ffn_mx_decode(fmt, x2, keys, values, bias, act, bins.offsets, bins.perm, bins.K)
             ctx.saved = None                     # no backward can follow
             return ops.combine(y, bins, idx, w, combine_mode, T)
         return MoEFFNPackedFP8._forward(ctx, x2, w, idx, bins, keys, values, bias, act, combine_mode, cache, wgrad_fp8)
@@ -1682,9 +1664,9 @@ class DenseFFNFP8(_ForwardAware):
         T, D = x2.shape
         if (not _needs_backward(ctx) and cache and 0 < T <= ops.decode_rows() and x2.dtype == torch.bfloat16):
             x2 = x2.contiguous()
-            if _fp8_decode_ok(T, D, w1.shape[1], w2.shape[1]):         # the decode path of MoEFFNPackedFP8 with E = 1
-                ffn = _ffn_fp4_decode if fp4_decode and _fp4_decode_ok(T, D, w1.shape[1], w2.shape[1]) else _ffn_fp8_decode
-                return ffn(x2, w1, w2, b1, act, ops.dense_offsets(T, x2.device), None, 1)
+            fmt = _mx_decode_format(T, D, w1.shape[1], w2.shape[1], fp4_decode)
+            if fmt is not None:                                        # the decode path of MoEFFNPackedFP8 with E = 1
+                return _ffn_mx_decode(fmt, x2, w1, w2, b1, act, ops.dense_offsets(T, x2.device), None, 1)
         y, saved, ctx.cfg = dense_ffn_fp8_forward(x2, w1, b1, w2, act, cache)
         ctx.save_for_backward(*saved)
         ctx.wgrad_fp8 = bool(wgrad_fp8)

@@ -2,6 +2,7 @@
 current HIP stream.  No math happens here."""
 from __future__ import annotations
 
+import collections
 import os
 from typing import Optional, Sequence
 
@@ -731,7 +732,7 @@ def grouped_gemm(A: torch.Tensor, b_ptrs: torch.Tensor, b_layout: int, ldb: int,
 
 # ------------------------------------------------------------------------------------------------ decode path (few rows)
 # Largest number of routed rows (T * K) a forward-only call may have to take the weight-streaming grouped GEMM (csrc/gemm_skinny.hip;
-# csrc/gemm_skinny_fp8.hip in the fp8 layers)
+# csrc/gemm_skinny_mx.hip in the fp8 layers)
 # instead of dispatch + the tiled kernels.  0 = off (the default): every call does exactly what it does without the switch.  Seeded
 # once from CSMOE_DECODE_ROWS; competesmoe_amd.decode_rows(n) sets it.
 _DECODE_ROWS = max(0, int(os.environ.get("CSMOE_DECODE_ROWS", "0") or 0))
@@ -1137,15 +1138,78 @@ def grouped_gemm_mxfp8(Aq: torch.Tensor, As: torch.Tensor, Bq: torch.Tensor, Bs:
     return (Cm, C2) if want_c2 else Cm
 
 
+# The two weight formats of the MX decode GEMM (csrc/gemm_skinny_mx.hip): the tag in messages and profiles, the library entry and
+# its `_ok` query, the weight elements per byte of a table row, and what the operands hold
+_SkinnyMx = collections.namedtuple("_SkinnyMx", "tag entry ok_entry k_per_byte operands")
+_SKINNY_MXFP8 = _SkinnyMx("grouped_gemm_skinny_mxfp8", "csmoe_grouped_gemm_skinny_mxfp8", "csmoe_grouped_gemm_skinny_mxfp8_ok", 1,
+                          "e4m3 elements, e8m0 scales")
+_SKINNY_MXFP4W = _SkinnyMx("grouped_gemm_skinny_mxfp4w", "csmoe_grouped_gemm_skinny_mxfp4w", "csmoe_grouped_gemm_skinny_mxfp4w_ok", 2,
+                           "e4m3 rows, packed e2m1 weights, e8m0 scales")
+
+
+def _skinny_mx_ok(f, M, N, Kd, lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, epilogue, quant_out) -> bool:
+    ks = Kd // 32                                                    # leading dimensions default to those of contiguous operands
+    return bool(getattr(lib, f.ok_entry)(
+        M, N, Kd, Kd if lda is None else int(lda), ks if ldas is None else int(ldas), Kd // f.k_per_byte if ldb is None else int(ldb),
+        ks if ldbs is None else int(ldbs), N if ldc is None else int(ldc), N if ldcq is None else int(ldcq),
+        N // 32 if ldcs is None else int(ldcs), epilogue, int(bool(quant_out))))
+
+
+def _skinny_mx(f, Aq, As, Bq, Bs, offsets, bias_ptrs, epilogue, act, want_c, want_c2, want_q, src_rows, src_div, out, out2, out_q,
+               out_s):
+    _need_cuda(Aq, As, Bq, Bs, offsets, src_rows)
+    if Aq.stride(1) != 1 or As.stride(1) != 1 or not Bq.is_contiguous() or not Bs.is_contiguous():
+        raise ValueError(f"csmoe {f.tag}: Aq / As need unit column stride, Bq / Bs must be contiguous")
+    if Aq.dtype != torch.uint8 or As.dtype != torch.uint8 or Bq.dtype != torch.uint8 or Bs.dtype != torch.uint8:
+        raise ValueError(f"csmoe {f.tag}: operands are uint8 ({f.operands})")
+    Kd = Aq.shape[1]
+    E, N, _ = Bq.shape
+    ldb = Kd // f.k_per_byte                                         # bytes of a weight row
+    if Bq.shape[2] * f.k_per_byte != Kd or As.shape != (Aq.shape[0], Kd // 32) or Bs.shape != (E, N, Kd // 32):
+        raise ValueError(f"csmoe {f.tag}: operand shapes do not match")
+    if src_rows is not None and (src_rows.dtype != torch.int32 or not src_rows.is_contiguous()):
+        raise ValueError(f"csmoe {f.tag}: src_rows must be a contiguous int32 vector")
+    M = Aq.shape[0] if src_rows is None else src_rows.numel()
+    dev = Aq.device
+    ldc = N
+    for o in (out, out2):
+        if o is not None:
+            if o.shape != (M, N) or o.dtype != torch.bfloat16 or o.stride(1) != 1:
+                raise ValueError(f"csmoe {f.tag}: `out` / `out2` must be bf16 [M, N] with unit column stride")
+            ldc = o.stride(0)
+    if out is not None and out2 is not None and out.stride(0) != out2.stride(0):
+        raise ValueError(f"csmoe {f.tag}: `out` and `out2` share one row stride")
+    if (out_q is None) != (out_s is None):
+        raise ValueError(f"csmoe {f.tag}: `out_q` and `out_s` go together")
+    if out_q is not None and (out_q.shape != (M, N) or out_s.shape != (M, N // 32) or out_q.dtype != torch.uint8
+                              or out_s.dtype != torch.uint8 or out_q.stride(1) != 1 or out_s.stride(1) != 1):
+        raise ValueError(f"csmoe {f.tag}: `out_q` [M, N] / `out_s` [M, N/32] must be uint8 with unit column stride")
+    Cm = out if out is not None else (torch.empty(M, N, dtype=torch.bfloat16, device=dev) if want_c else None)
+    C2 = out2 if out2 is not None else (torch.empty(M, N, dtype=torch.bfloat16, device=dev) if want_c2 else None)
+    q, s = out_q, out_s
+    if q is None and want_q:
+        q = torch.empty(M, N, dtype=torch.uint8, device=dev)
+        s = torch.empty(M, N // 32, dtype=torch.uint8, device=dev)
+    bq = ptr_table(Bq, E, N * ldb)
+    bs = ptr_table(Bs, E, N * (Kd // 32))
+    entry = getattr(lib, f.entry)
+    with _timed(f.tag, 2.0 * M * N * Kd):
+        L.check(entry(Aq.data_ptr(), Aq.stride(0), As.data_ptr(), As.stride(0), _ptr(src_rows), int(src_div), bq.data_ptr(),
+                      bs.data_ptr(), ldb, Kd // 32, _ptr(bias_ptrs), offsets.data_ptr(), E, M, N, Kd, _ptr(Cm), _ptr(C2), ldc, _ptr(q),
+                      _ptr(s), q.stride(0) if q is not None else N, s.stride(0) if s is not None else N // 32, epilogue, act,
+                      _stream()), f.tag)
+    if q is not None:
+        return Cm, C2, q, s
+    return (Cm, C2) if (want_c2 or out2 is not None) else Cm
+
+
 def grouped_gemm_skinny_mxfp8_ok(M: int, N: int, Kd: int, lda: Optional[int] = None, ldas: Optional[int] = None,
-                                ldb: Optional[int] = None, ldbs: Optional[int] = None, ldc: Optional[int] = None,
-                                ldcq: Optional[int] = None, ldcs: Optional[int] = None, epilogue: int = L.EPI_PLAIN,
-                                quant_out: bool = False) -> bool:
+                                 ldb: Optional[int] = None, ldbs: Optional[int] = None, ldc: Optional[int] = None,
+                                 ldcq: Optional[int] = None, ldcs: Optional[int] = None, epilogue: int = L.EPI_PLAIN,
+                                 quant_out: bool = False) -> bool:
     """Does csmoe_grouped_gemm_skinny_mxfp8 take this launch (forward epilogue, Kd % 128, N % 8 -- % 32 with the quantised output --
     and the alignment / 2 GiB rule)?  Leading dimensions default to those of contiguous operands."""
-    d = lambda v, dflt: dflt if v is None else int(v)
-    return bool(lib.csmoe_grouped_gemm_skinny_mxfp8_ok(M, N, Kd, d(lda, Kd), d(ldas, Kd // 32), d(ldb, Kd), d(ldbs, Kd // 32), d(ldc, N),
-                                                       d(ldcq, N), d(ldcs, N // 32), epilogue, int(bool(quant_out))))
+    return _skinny_mx_ok(_SKINNY_MXFP8, M, N, Kd, lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, epilogue, quant_out)
 
 
 def grouped_gemm_skinny_mxfp8(Aq: torch.Tensor, As: torch.Tensor, Bq: torch.Tensor, Bs: torch.Tensor, offsets: torch.Tensor,
@@ -1160,118 +1224,34 @@ def grouped_gemm_skinny_mxfp8(Aq: torch.Tensor, As: torch.Tensor, Bq: torch.Tens
     bf16-rounded activated output, the bytes quantize_mxfp8(C2) would give; C and C2 may both be left out then.  `out` / `out2` /
     `out_q` / `out_s`: views (unit column stride; out and out2 share a row stride) to write into instead of new tensors.
     Returns C, or the tuple (C, C2) / (C, C2, q, s) of what was asked for, None where not."""
-    _need_cuda(Aq, As, Bq, Bs, offsets, src_rows)
-    if Aq.stride(1) != 1 or As.stride(1) != 1 or not Bq.is_contiguous() or not Bs.is_contiguous():
-        raise ValueError("csmoe grouped_gemm_skinny_mxfp8: Aq / As need unit column stride, Bq / Bs must be contiguous")
-    if Aq.dtype != torch.uint8 or As.dtype != torch.uint8 or Bq.dtype != torch.uint8 or Bs.dtype != torch.uint8:
-        raise ValueError("csmoe grouped_gemm_skinny_mxfp8: operands are uint8 (e4m3 elements, e8m0 scales)")
-    Kd = Aq.shape[1]
-    E, N, _ = Bq.shape
-    if Bq.shape[2] != Kd or As.shape != (Aq.shape[0], Kd // 32) or Bs.shape != (E, N, Kd // 32):
-        raise ValueError("csmoe grouped_gemm_skinny_mxfp8: operand shapes do not match")
-    if src_rows is not None and (src_rows.dtype != torch.int32 or not src_rows.is_contiguous()):
-        raise ValueError("csmoe grouped_gemm_skinny_mxfp8: src_rows must be a contiguous int32 vector")
-    M = Aq.shape[0] if src_rows is None else src_rows.numel()
-    dev = Aq.device
-    ldc = N
-    for o in (out, out2):
-        if o is not None:
-            if o.shape != (M, N) or o.dtype != torch.bfloat16 or o.stride(1) != 1:
-                raise ValueError("csmoe grouped_gemm_skinny_mxfp8: `out` / `out2` must be bf16 [M, N] with unit column stride")
-            ldc = o.stride(0)
-    if out is not None and out2 is not None and out.stride(0) != out2.stride(0):
-        raise ValueError("csmoe grouped_gemm_skinny_mxfp8: `out` and `out2` share one row stride")
-    if (out_q is None) != (out_s is None):
-        raise ValueError("csmoe grouped_gemm_skinny_mxfp8: `out_q` and `out_s` go together")
-    if out_q is not None and (out_q.shape != (M, N) or out_s.shape != (M, N // 32) or out_q.dtype != torch.uint8
-                              or out_s.dtype != torch.uint8 or out_q.stride(1) != 1 or out_s.stride(1) != 1):
-        raise ValueError("csmoe grouped_gemm_skinny_mxfp8: `out_q` [M, N] / `out_s` [M, N/32] must be uint8 with unit column stride")
-    Cm = out if out is not None else (torch.empty(M, N, dtype=torch.bfloat16, device=dev) if want_c else None)
-    C2 = out2 if out2 is not None else (torch.empty(M, N, dtype=torch.bfloat16, device=dev) if want_c2 else None)
-    q, s = out_q, out_s
-    if q is None and want_q:
-        q = torch.empty(M, N, dtype=torch.uint8, device=dev)
-        s = torch.empty(M, N // 32, dtype=torch.uint8, device=dev)
-    bq = ptr_table(Bq, E, N * Kd)
-    bs = ptr_table(Bs, E, N * (Kd // 32))
-    with _timed("grouped_gemm_skinny_mxfp8", 2.0 * M * N * Kd):
-        L.check(lib.csmoe_grouped_gemm_skinny_mxfp8(Aq.data_ptr(), Aq.stride(0), As.data_ptr(), As.stride(0), _ptr(src_rows), int(src_div),
-                                                    bq.data_ptr(), bs.data_ptr(), Kd, Kd // 32, _ptr(bias_ptrs), offsets.data_ptr(), E, M,
-                                                    N, Kd, _ptr(Cm), _ptr(C2), ldc, _ptr(q), _ptr(s),
-                                                    q.stride(0) if q is not None else N, s.stride(0) if s is not None else N // 32,
-                                                    epilogue, act, _stream()), "grouped_gemm_skinny_mxfp8")
-    if q is not None:
-        return Cm, C2, q, s
-    return (Cm, C2) if (want_c2 or out2 is not None) else Cm
+    return _skinny_mx(_SKINNY_MXFP8, Aq, As, Bq, Bs, offsets, bias_ptrs, epilogue, act, want_c, want_c2, want_q, src_rows, src_div, out,
+                      out2, out_q, out_s)
 
 
 def grouped_gemm_skinny_mxfp4w_ok(M: int, N: int, Kd: int, lda: Optional[int] = None, ldas: Optional[int] = None,
-                                ldb: Optional[int] = None, ldbs: Optional[int] = None, ldc: Optional[int] = None,
-                                ldcq: Optional[int] = None, ldcs: Optional[int] = None, epilogue: int = L.EPI_PLAIN,
-                                quant_out: bool = False) -> bool:
+                                  ldb: Optional[int] = None, ldbs: Optional[int] = None, ldc: Optional[int] = None,
+                                  ldcq: Optional[int] = None, ldcs: Optional[int] = None, epilogue: int = L.EPI_PLAIN,
+                                  quant_out: bool = False) -> bool:
     """Does csmoe_grouped_gemm_skinny_mxfp4w take this launch (forward epilogue, Kd % 128, N % 8 -- % 32 with the quantised output --
     and the alignment / 2 GiB rule)?  Leading dimensions default to those of contiguous operands; `ldb` counts bytes of a packed
     weight row (Kd / 2)."""
-    d = lambda v, dflt: dflt if v is None else int(v)
-    return bool(lib.csmoe_grouped_gemm_skinny_mxfp4w_ok(M, N, Kd, d(lda, Kd), d(ldas, Kd // 32), d(ldb, Kd // 2), d(ldbs, Kd // 32), d(ldc, N),
-                                                       d(ldcq, N), d(ldcs, N // 32), epilogue, int(bool(quant_out))))
+    return _skinny_mx_ok(_SKINNY_MXFP4W, M, N, Kd, lda, ldas, ldb, ldbs, ldc, ldcq, ldcs, epilogue, quant_out)
 
 
 def grouped_gemm_skinny_mxfp4w(Aq: torch.Tensor, As: torch.Tensor, Bq: torch.Tensor, Bs: torch.Tensor, offsets: torch.Tensor,
-                              bias_ptrs: Optional[torch.Tensor] = None, epilogue: int = L.EPI_PLAIN, act: int = L.ACT_NONE,
-                              want_c: bool = True, want_c2: bool = False, want_q: bool = False,
-                              src_rows: Optional[torch.Tensor] = None, src_div: int = 1, out: Optional[torch.Tensor] = None,
-                              out2: Optional[torch.Tensor] = None, out_q: Optional[torch.Tensor] = None,
-                              out_s: Optional[torch.Tensor] = None):
+                               bias_ptrs: Optional[torch.Tensor] = None, epilogue: int = L.EPI_PLAIN, act: int = L.ACT_NONE,
+                               want_c: bool = True, want_c2: bool = False, want_q: bool = False,
+                               src_rows: Optional[torch.Tensor] = None, src_div: int = 1, out: Optional[torch.Tensor] = None,
+                               out2: Optional[torch.Tensor] = None, out_q: Optional[torch.Tensor] = None,
+                               out_s: Optional[torch.Tensor] = None):
     """csmoe_grouped_gemm_skinny_mxfp4w: grouped_gemm_skinny_mxfp8 with MXFP4 weights (W4A8; forward epilogues).  Aq [R, Kd] /
     As [R, Kd/32] MXFP8 as there; Bq [E, N, Kd/2] packed e2m1 (quantize_mxfp4) / Bs [E, N, Kd/32] uint8; `src_rows` (int32 [M]): output row m reads row
     src_rows[m] // src_div of Aq AND As.  `want_q` (EPI_BIAS_ACT): also the MXFP8 quantisation (q [M, N], s [M, N/32]) of the
     bf16-rounded activated output, the bytes quantize_mxfp8(C2) would give; C and C2 may both be left out then.  `out` / `out2` /
     `out_q` / `out_s`: views (unit column stride; out and out2 share a row stride) to write into instead of new tensors.
     Returns C, or the tuple (C, C2) / (C, C2, q, s) of what was asked for, None where not."""
-    _need_cuda(Aq, As, Bq, Bs, offsets, src_rows)
-    if Aq.stride(1) != 1 or As.stride(1) != 1 or not Bq.is_contiguous() or not Bs.is_contiguous():
-        raise ValueError("csmoe grouped_gemm_skinny_mxfp4w: Aq / As need unit column stride, Bq / Bs must be contiguous")
-    if Aq.dtype != torch.uint8 or As.dtype != torch.uint8 or Bq.dtype != torch.uint8 or Bs.dtype != torch.uint8:
-        raise ValueError("csmoe grouped_gemm_skinny_mxfp4w: operands are uint8 (e4m3 rows, packed e2m1 weights, e8m0 scales)")
-    Kd = Aq.shape[1]
-    E, N, _ = Bq.shape
-    if Bq.shape[2] * 2 != Kd or As.shape != (Aq.shape[0], Kd // 32) or Bs.shape != (E, N, Kd // 32):
-        raise ValueError("csmoe grouped_gemm_skinny_mxfp4w: operand shapes do not match")
-    if src_rows is not None and (src_rows.dtype != torch.int32 or not src_rows.is_contiguous()):
-        raise ValueError("csmoe grouped_gemm_skinny_mxfp4w: src_rows must be a contiguous int32 vector")
-    M = Aq.shape[0] if src_rows is None else src_rows.numel()
-    dev = Aq.device
-    ldc = N
-    for o in (out, out2):
-        if o is not None:
-            if o.shape != (M, N) or o.dtype != torch.bfloat16 or o.stride(1) != 1:
-                raise ValueError("csmoe grouped_gemm_skinny_mxfp4w: `out` / `out2` must be bf16 [M, N] with unit column stride")
-            ldc = o.stride(0)
-    if out is not None and out2 is not None and out.stride(0) != out2.stride(0):
-        raise ValueError("csmoe grouped_gemm_skinny_mxfp4w: `out` and `out2` share one row stride")
-    if (out_q is None) != (out_s is None):
-        raise ValueError("csmoe grouped_gemm_skinny_mxfp4w: `out_q` and `out_s` go together")
-    if out_q is not None and (out_q.shape != (M, N) or out_s.shape != (M, N // 32) or out_q.dtype != torch.uint8
-                              or out_s.dtype != torch.uint8 or out_q.stride(1) != 1 or out_s.stride(1) != 1):
-        raise ValueError("csmoe grouped_gemm_skinny_mxfp4w: `out_q` [M, N] / `out_s` [M, N/32] must be uint8 with unit column stride")
-    Cm = out if out is not None else (torch.empty(M, N, dtype=torch.bfloat16, device=dev) if want_c else None)
-    C2 = out2 if out2 is not None else (torch.empty(M, N, dtype=torch.bfloat16, device=dev) if want_c2 else None)
-    q, s = out_q, out_s
-    if q is None and want_q:
-        q = torch.empty(M, N, dtype=torch.uint8, device=dev)
-        s = torch.empty(M, N // 32, dtype=torch.uint8, device=dev)
-    bq = ptr_table(Bq, E, N * (Kd // 2))
-    bs = ptr_table(Bs, E, N * (Kd // 32))
-    with _timed("grouped_gemm_skinny_mxfp4w", 2.0 * M * N * Kd):
-        L.check(lib.csmoe_grouped_gemm_skinny_mxfp4w(Aq.data_ptr(), Aq.stride(0), As.data_ptr(), As.stride(0), _ptr(src_rows), int(src_div),
-                                                    bq.data_ptr(), bs.data_ptr(), Kd // 2, Kd // 32, _ptr(bias_ptrs), offsets.data_ptr(), E, M,
-                                                    N, Kd, _ptr(Cm), _ptr(C2), ldc, _ptr(q), _ptr(s),
-                                                    q.stride(0) if q is not None else N, s.stride(0) if s is not None else N // 32,
-                                                    epilogue, act, _stream()), "grouped_gemm_skinny_mxfp4w")
-    if q is not None:
-        return Cm, C2, q, s
-    return (Cm, C2) if (want_c2 or out2 is not None) else Cm
+    return _skinny_mx(_SKINNY_MXFP4W, Aq, As, Bq, Bs, offsets, bias_ptrs, epilogue, act, want_c, want_c2, want_q, src_rows, src_div, out,
+                      out2, out_q, out_s)
 
 
 def dense_gemm_mxfp8(Aq: torch.Tensor, As: torch.Tensor, Bq: torch.Tensor, Bs: torch.Tensor, bias: Optional[torch.Tensor] = None,

@@ -98,7 +98,7 @@ class MoE(LoggingLayer, RegularizedLayer, OncePerIterLayer, nn.Module):
         if self.fp8_wgrad and not self.fp8_experts:
             raise ValueError("competesmoe_amd: args.fp8_wgrad (or CSMOE_FP8_WGRAD=1) needs args.fp8_experts")
         # W4A8 decode: where the fp8 decode path would run (forward-only, fp8_weight_cache, at most decode_rows() routed rows), the
-        # expert weights are MXFP4 tables (functional._ffn_fp4_decode); every other call is unchanged.  Off by default
+        # expert weights are MXFP4 tables (functional._ffn_mx_decode); every other call is unchanged.  Off by default
         self.fp4_decode_weights = bool(getattr(args, "fp4_decode_weights", False))
         if self.fp4_decode_weights and not self.fp8_experts:
             raise ValueError("competesmoe_amd: args.fp4_decode_weights is the 4-bit weight form of the fp8 decode path: it needs "

@@ -522,7 +522,7 @@ int csmoe_dense_gemm_mxfp8_q(const void* Aq, int64_t lda, const void* As, int64_
                              int epilogue, int act, void* Cq, int64_t ldcq, void* Cs, int64_t ldcs, csmoe_stream_t stream);
 int csmoe_gemm_mxfp8_q_ok(int M, int N, int Kd, int64_t lda, int64_t ldas, int64_t ldb, int64_t ldbs, int64_t ldc, int64_t ldcq,
                           int64_t ldcs, int epilogue, int quant_out, int dense);
-/* Few-row (decode) form of csmoe_grouped_gemm_mxfp8 (csrc/gemm_skinny_fp8.hip): the weight streamer of csmoe_grouped_gemm_skinny
+/* Few-row (decode) form of csmoe_grouped_gemm_mxfp8 (csrc/gemm_skinny_mx.hip): the weight streamer of csmoe_grouped_gemm_skinny
  * on MXFP8 operands, one v_mfma_scale_f32_16x16x128_f8f6f4 per 128-element K-step, the weights (half the bytes of bf16) read once
  * per 16-row block straight into registers.  For every expert e and binned row m in [offsets[e], offsets[e+1])
  *     C[m, 0:N] = epilogue( sum_k dq(A)[row(m), k] dq(B_e)[n, k] ),   row(m) = src_rows ? src_rows[m] / src_div : m
@@ -563,7 +563,7 @@ int csmoe_grouped_gemm_skinny_mxfp8_ok(int M, int N, int Kd, int64_t lda, int64_
  * table of a master stored [Kd, N].  q 16-byte aligned (a block is one 16-byte store); else CSMOE_ERR_UNSUPPORTED. */
 int csmoe_quantize_mxfp4(const void* x, const void* const* x_ptrs, int E, int64_t ldx, int R, int C, int dtype, int transpose,
                          void* q, void* s, csmoe_stream_t stream);
-/* csmoe_grouped_gemm_skinny_mxfp8 with MXFP4 weights (csrc/gemm_skinny_fp4.hip): the same decomposition, gather (src_rows /
+/* csmoe_grouped_gemm_skinny_mxfp8 with MXFP4 weights (csrc/gemm_skinny_mx.hip, the same kernel text): the same decomposition, gather (src_rows /
  * src_div for elements and scale rows), epilogues (PLAIN, BIAS, BIAS_ACT at the same rounding points) and optional fused MXFP8
  * output Cq / Cs (byte for byte what csmoe_quantize_mxfp8 (transpose = 0) writes for C2).  For every expert e and binned row m
  *     C[m, 0:N] = epilogue( sum_k dq(A)[row(m), k] dq(B_e)[n, k] ),   row(m) = src_rows ? src_rows[m] / src_div : m

@@ -1,4 +1,4 @@
-"""The contract of csmoe_grouped_gemm_skinny_mxfp4w (csrc/gemm_skinny_fp4.hip) on exact data, bit for bit: the recipe of
+"""The contract of csmoe_grouped_gemm_skinny_mxfp4w (csrc/gemm_skinny_mx.hip) on exact data, bit for bit: the recipe of
 tests/test_skinny_fp8_contract_gpu.py with MXFP4 weights.
 
 A integers in [-2, 2] as e4m3 with scales 2^-2 .. 2^2, B drawn from {-1, 0, 1, 2} as e2m1 (packed two per byte) with scales
@@ -9,7 +9,7 @@ A integers in [-2, 2] as e4m3 with scales 2^-2 .. 2^2, B drawn from {-1, 0, 1, 2
 wrong nibble order, a wrong lane -> k map, a swapped operand role and a wrong scale byte.
 
 Shapes: expert row counts [0, 1, 16, 17, 3, 0, 33], i.e. 11 row blocks at most, so the launch takes the 64-column slab from
-ceil(N / 64) >= 24 on (256 workgroups: gemm_skinny_fp4.hip's slab rule).  N in {72, 200, 1464} without and {96, 224, 1440} with the
+ceil(N / 64) >= 24 on (256 workgroups: gemm_skinny_mx.hip's slab rule).  N in {72, 200, 1464} without and {96, 224, 1440} with the
 quantised output on the 32-column slab (1464 and 1440: 23 slabs of 64, the last N before the switch), N = 1480 without and 1504
 with it on the 64-column slab (24 slabs, the first after it); none is a multiple of 64, and 72 / 200 / 1464 none of 32.  Kd = 128
 (one K-step: seven waves contribute zero tiles), 1152 (nine steps dealt 2, 2, 2, 2, 1, 0, 0, 0: no unrolled iteration on either

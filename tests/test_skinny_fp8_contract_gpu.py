@@ -1,4 +1,4 @@
-"""The contract of csmoe_grouped_gemm_skinny_mxfp8 (csrc/gemm_skinny_fp8.hip) on exact data, bit for bit.
+"""The contract of csmoe_grouped_gemm_skinny_mxfp8 (csrc/gemm_skinny_mx.hip) on exact data, bit for bit.
 
 Recipe of tests/test_fp8_gpu.py::test_gemm_is_exact_on_exact_data: A integers in [-2, 2] and B integers in [-1, 2] as e4m3, A scales
 2^-2 .. 2^2 and B scales 2^-1 .. 2^1 that differ per row and per k-block, bf16 biases that are multiples of 2^-5 in [-2, 2].  A term

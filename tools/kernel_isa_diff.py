@@ -2,12 +2,14 @@
 """Compare the gfx950 device code of two source trees, kernel by kernel: the acceptance check of a refactor of the GEMM units.
 
     tools/kernel_isa_diff.py <old tree> <new tree> [unit ...]        # units: gemm_bf16_v2 gemm_fp8 ...; default: every csrc/*.hip
+    tools/kernel_isa_diff.py <old tree> <new tree> --units gemm_skinny_fp8+gemm_skinny_fp4=gemm_skinny_mx      # units that were merged
 
 Each unit of both trees is compiled with the FLAGS of its own tree's csrc/Makefile plus `--cuda-device-only -S`; comments and the
 per-build `__hip_cuid_*` symbol are dropped, the compiler's running function numbers in local labels are blanked, and the text
 of every device function (code, kernel descriptor, metadata record) is compared.  One line per function: `identical`,
 `DIFFERENT`, `removed` or `added`; exit status 1 if anything is DIFFERENT.  --map rewrites mangled names of the OLD tree
-before matching (a template parameter that went away); the gg8_kernel MODE parameter is built in.  --keep DIR keeps the
+before matching (a template parameter that went away); the gg8_kernel MODE parameter is built in.  --units OLD+OLD=NEW compares
+the new unit with the union of the named old ones, whose `(module data)` is reported as `merged` and not counted.  --keep DIR keeps the
 assembly there and reuses a listing that is newer than its tree's sources.  It compares two builds with each other and nothing
 else."""
 import argparse, concurrent.futures, difflib, os, re, subprocess, sys, tempfile
@@ -94,6 +96,7 @@ def main():
     ap.add_argument("old"), ap.add_argument("new"), ap.add_argument("units", nargs="*")
     ap.add_argument("-j", "--jobs", type=int, default=min(MAX_JOBS, os.cpu_count() or 1))
     ap.add_argument("--map", action="append", default=[], metavar="REGEX=REPL", help="rewrite names of the old tree")
+    ap.add_argument("--units", dest="merged", action="append", default=[], metavar="OLD+OLD=NEW", help="old units merged into a new one")
     ap.add_argument("--keep", metavar="DIR", help="keep (and reuse) the assembly listings here")
     ap.add_argument("--show", type=int, default=0, metavar="N", help="print the first N diff lines of a DIFFERENT function")
     a = ap.parse_args()
@@ -101,14 +104,19 @@ def main():
         sorted(f[:-4] for f in os.listdir(csrc(a.new)) if f.endswith(".hip"))
     work = a.keep or tempfile.mkdtemp(prefix="isa_diff_")
     maps = BUILTIN_MAPS + [tuple(m.split("=", 1)) for m in a.map]
-    jobs = [(t, u, os.path.join(work, side, u + ".s")) for u in units for side, t in (("old", a.old), ("new", a.new))]
+    merged = {new: old.split("+") for old, new in (m.split("=", 1) for m in a.merged)}
+    jobs = [(a.new, u, os.path.join(work, "new", u + ".s")) for u in units] + \
+        [(a.old, o, os.path.join(work, "old", o + ".s")) for u in units for o in merged.get(u, [u])]
     for side in ("old", "new"):
         os.makedirs(os.path.join(work, side), exist_ok=True)
     with concurrent.futures.ThreadPoolExecutor(max(1, min(a.jobs, MAX_JOBS))) as ex:
         list(ex.map(lambda j: compile_unit(*j), jobs))
     bad = 0
     for u in units:
-        old = functions(os.path.join(work, "old", u + ".s"), maps)
+        old = {}
+        for o in merged.get(u, [u]):
+            for n, text in functions(os.path.join(work, "old", o + ".s"), maps).items():
+                old.setdefault(n, []).extend(text)
         new = functions(os.path.join(work, "new", u + ".s"), [])
         names = list(dict.fromkeys(list(old) + list(new)))
         pretty = demangle(names)
@@ -117,6 +125,8 @@ def main():
                 verdict = "removed" if n in old else "added"
             else:
                 verdict = "identical" if old[n] == new[n] else "DIFFERENT"
+            if verdict == "DIFFERENT" and u in merged and n == "(module data)":
+                verdict = "merged"                  # the old units' records one after the other: shown, not counted
             bad += verdict == "DIFFERENT"
             lines = f"{len(new[n]) if n in new else len(old[n])} lines"
             print(f"{u:18s} {verdict:10s} {pretty[n]}  ({lines})")
